@@ -6,13 +6,17 @@ add, smooth field, metric/RMS reduction) on a 512x512x256 fp32 volume pair that 
 resident in HBM -- the finest pyramid level of config 2, where 98 % of the reference's voxel
 iterations are spent.  `value` = voxels x steps x ranks / wall time, in Mvoxels/s.
 
-  python bench.py [--gpus N --steps K --warmup W]            (N > 1: launched by torch.distributed.run)
+  python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]   (N > 1: launched by torch.distributed.run)
 
 N > 1 is the multi-atlas shape of the path: every rank registers its own atlas to the target with
 no data-path collective inside the demons loop (weak scaling); timing is barrier-bracketed and the
-maximum over ranks.  Extra keys: `roofline` (dominant kernel, algorithmic bytes / HIP-event time),
-`cpu_baseline` (the oracle timed on this host's cores, rank 0, N == 1 only), `kernels` (per-kernel
-breakdown) and `registration_s` (one whole 3-level config-2 registration through the drop-in API).
+maximum over ranks.  A plain run sets up, warms up, times one block of exactly K steps and prints
+the line.  `--dump-outputs DIR` then writes the displacement field of the last timed step (a fixed,
+seeded sample of rank 0's voxels) as DIR/*.npy.  `--full` adds everything else: the timed block is
+run --repeats times (median reported) with per-kernel HIP events, and the line gains `roofline`
+(dominant kernel, algorithmic bytes / HIP-event time), `kernels` (per-kernel breakdown),
+`registration_s` (one whole 3-level config-2 registration through the drop-in API), the multi-atlas
+legs and `cpu_baseline` (the oracle timed on this host's cores, rank 0, N == 1 only).
 """
 import argparse
 import json
@@ -281,6 +285,97 @@ def cpu_baseline(fixed, moving, spacing, budget_s=15.0):
                       ("" if kind == "reference" else " (SimpleITK unavailable: C/OpenMP fp64 restatement stands in)")}
 
 
+DUMP_SAMPLE_VOXELS = 1 << 20     # 12 MB of field values and 8 MB of indices: well under the 64 MB a dump may take
+DUMP_SAMPLE_SEED = 0
+
+
+def dump_outputs(out_dir, field):
+    """--dump-outputs: what a caller of the timed path receives after its last step -- the displacement field that
+    pp_demons_execute_f32 leaves in `field` ([3, Z, Y, X] fp32, mm) -- at a fixed, seeded sample of voxels (every voxel when the
+    volume has fewer), so that two builds can be compared output for output.  Writes
+      displacement_field_sample.npy        float32 [3, n]: the field's x, y, z components at the sampled voxels
+      displacement_field_sample_index.npy  float64 [n]: their flat [Z, Y, X] indices, ascending
+    and returns {name: shape}."""
+    import numpy as np
+
+    nvox = field[0].numel()
+    if nvox <= DUMP_SAMPLE_VOXELS:
+        idx = np.arange(nvox, dtype=np.int64)
+    else:
+        idx = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(nvox, DUMP_SAMPLE_VOXELS, replace=False))
+    sample = field.reshape(3, nvox)[:, torch.from_numpy(idx).to(field.device)].to(device="cpu", dtype=torch.float32).numpy()
+    arrays = {"displacement_field_sample": sample, "displacement_field_sample_index": idx.astype(np.float64)}
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return {name: list(a.shape) for name, a in arrays.items()}
+
+
+def kernel_report(prof, event_pair_ms, args, size, ms_per_step):
+    """--full: the per-kernel HIP-event figures of the timed blocks, the roofline of the dominant kernel and of the whole
+    iteration -> keys of the bench line."""
+    nx, ny, nz = size
+    nvox = nx * ny * nz
+    kernels = {}
+    for name, (launches, total_ms) in prof.items():
+        if launches == 0:
+            continue
+        avg_ms = total_ms / launches
+        cb, kb = COMPULSORY_BYTES.get(name), CONTRACT_BYTES.get(name)
+        kernels[name] = {"launches": launches, "avg_ms": avg_ms,
+                         "compulsory_bytes_per_voxel": cb,
+                         "compulsory_GBps": (cb * nvox / (avg_ms * 1e-3) / 1e9) if cb else None,
+                         "frac_of_peak": (cb * nvox / (avg_ms * 1e-3) / 1e9 / HBM_PEAK_GBS) if cb else None,
+                         "contract_bytes_per_voxel": kb,
+                         "contract_GBps": (kb * nvox / (avg_ms * 1e-3) / 1e9) if kb else None}
+    dom = max(kernels, key=lambda k: kernels[k]["avg_ms"] * kernels[k]["launches"]) if kernels else None
+    # Measured HBM-side traffic of the same kernels: rocprofv3 --pmc passes of THIS command (tools/gpu_final.sh ->
+    # profiles/round<N>_pmc.json, which names the commit and the raw counter file it was reduced from; FETCH_SIZE
+    # calibrated as MI355X_MICROARCH.md prescribes).  Counters cannot be read inside an untraced run, so the figure
+    # is attached only when the committed capture is of this size and these kernels.
+    pmc = load_pmc(nx, ny, nz)
+    if pmc:
+        for name, k in kernels.items():
+            tb = pmc.get("hbm_bytes_per_launch", {}).get(name)
+            if tb:
+                k["traffic_bytes_per_voxel"] = tb / nvox
+                k["traffic_GBps"] = tb / (k["avg_ms"] * 1e-3) / 1e9
+    roofline = None
+    if dom and kernels[dom]["compulsory_GBps"]:
+        a = kernels[dom]["compulsory_GBps"]
+        traffic = pmc.get("hbm_bytes_per_launch", {}).get(dom) if pmc else None
+        roofline = {"bound": "hbm", "kernel": dom, "achieved": a, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                    "frac": a / HBM_PEAK_GBS, "traffic": traffic,
+                    "traffic_source": ({"file": pmc.get("_file"), "commit": pmc.get("commit"), "raw": pmc.get("raw"),
+                                        "kernel_source_sha16": pmc.get("kernel_source_sha16")} if traffic else
+                                       {"note": "no committed PMC capture of these kernel sources (sha %s)" % kernel_source_sha16()}),
+                    "bytes_model": "compulsory (inputs once + outputs once of the schedule that runs)",
+                    "algorithmic_bytes_per_launch": kernels[dom]["compulsory_bytes_per_voxel"] * nvox,
+                    "avg_launch_ms": kernels[dom]["avg_ms"],
+                    "contract_model": {"bytes_per_voxel": kernels[dom]["contract_bytes_per_voxel"],
+                                       "GBps": kernels[dom]["contract_GBps"],
+                                       "note": "SURVEY 8(d) counts separable passes the fused kernel does not perform; "
+                                               "not a bandwidth"}}
+    fused_run = any(k.startswith("k_fused") for k in kernels)
+    iter_bytes = COMPULSORY_BYTES_ITER_FUSED if fused_run else CONTRACT_BYTES_ITER
+    iter_gbps = iter_bytes * nvox / (ms_per_step * 1e-3) / 1e9
+    return {
+        # HIP events bracket every K-th launch of each kernel inside the timed region (kernels[*].launches = bracketed launches)
+        "kernel_events_every": (None if args.no_kernel_events else max(1, args.kernel_events_every)),
+        "kernel_event_pair_ms": event_pair_ms,
+        "kernel_events_note": "kernels[*].avg_ms (and roofline.avg_launch_ms) are HIP event-to-event times on the launch stream: each "
+                              "includes the bracket's own cost (kernel_event_pair_ms: an empty bracket on this stream) and the lost "
+                              "back-to-back overlap, so they are upper bounds of the kernel durations rocprofv3 reports and may sum to "
+                              "more than ms_per_step; roofline.frac is therefore conservative",
+        "roofline": roofline,
+        "roofline_iteration": {"achieved": iter_gbps, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": iter_gbps / HBM_PEAK_GBS,
+                               "compulsory_bytes_per_voxel": iter_bytes,
+                               "contract_bytes_per_voxel": CONTRACT_BYTES_ITER,
+                               "contract_model_GBps": CONTRACT_BYTES_ITER * nvox / (ms_per_step * 1e-3) / 1e9},
+        "kernels": kernels,
+    }
+
+
 class Ranks:
     """The N > 1 skeleton of the bench (one process per GPU, launched by torch.distributed.run): process group, barrier,
     max-over-ranks and a gather of every rank's own time.  `backend` "nccl" is RCCL on ROCm; "gloo" exists so that the
@@ -409,20 +504,31 @@ def main():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--size", type=int, nargs=3, default=[512, 512, 256], metavar=("NX", "NY", "NZ"))
     ap.add_argument("--variant", choices=["auto", "fused", "staged"], default="auto")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-registration", action="store_true")
-    ap.add_argument("--no-atlas", action="store_true")
-    ap.add_argument("--no-kernel-events", action="store_true", help="time the region without the per-launch HIP events (no roofline block)")
-    ap.add_argument("--kernel-events-every", type=int, default=5, metavar="K",
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write the displacement field of the last one (rank 0; a fixed, seeded sample of "
+                         f"{DUMP_SAMPLE_VOXELS} voxels) as DIR/displacement_field_sample.npy (float32) and its voxel indices as "
+                         "DIR/displacement_field_sample_index.npy (float64); git ignores DIR = bench_outputs")
+    ap.add_argument("--full", action="store_true",
+                    help="measure everything around the headline too: --repeats timed blocks with per-kernel HIP events (roofline, "
+                         "kernels), one whole registration, the multi-atlas legs and the CPU baseline; without it the run times one "
+                         "block of --steps iterations and nothing else")
+    ap.add_argument("--pmc-calibration", action="store_true",
+                    help="first run two kernels with known byte counts (16 B/lane and 4 B/lane), so that a rocprofv3 --pmc pass of this "
+                         "command can calibrate FETCH_SIZE / WRITE_SIZE as MI355X_MICROARCH.md prescribes (tools/gpu_final.sh)")
+    fa = ap.add_argument_group("with --full (no effect without it)")
+    fa.add_argument("--no-cpu-baseline", action="store_true")
+    fa.add_argument("--no-registration", action="store_true")
+    fa.add_argument("--no-atlas", action="store_true")
+    fa.add_argument("--no-kernel-events", action="store_true", help="time the region without the per-launch HIP events (no roofline block)")
+    fa.add_argument("--kernel-events-every", type=int, default=5, metavar="K",
                     help="bracket every K-th launch of each kernel with HIP events inside the timed region (a pair of events costs the "
                          "stream ~7 us, 1.4 %% of a 0.5 ms kernel: with K = 5 the timed region carries a fifth of that and `avg_launch_ms` "
                          "is the mean of steps * repeats / K bracketed launches per kernel); 1 brackets every launch")
-    ap.add_argument("--repeats", type=int, default=5, help="the timed block of --steps iterations is run this many times; `value` and "
+    fa.add_argument("--repeats", type=int, default=5, help="the timed block of --steps iterations is run this many times; `value` and "
                     "`ms_per_step` are the MEDIAN block's, min / max are reported beside it (boxes differ by several per cent run to run)")
-    ap.add_argument("--pmc-calibration", action="store_true",
-                    help="first run two kernels with known byte counts (16 B/lane and 4 B/lane), so that a rocprofv3 --pmc pass of this "
-                         "command can calibrate FETCH_SIZE / WRITE_SIZE as MI355X_MICROARCH.md prescribes (tools/gpu_pmc2.sh)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     # `python bench.py --gpus N` started plainly -- the way the driver starts N = 1 -- launches itself: one process per GPU
     # under torch.distributed.run on this node (the driver's own N > 1 command sets WORLD_SIZE and comes straight through).
@@ -474,77 +580,38 @@ def main():
         p.iterations = args.warmup
         ctx.demons_execute(fixed, moving, geom, p, field, want_stats=False)
     torch.cuda.synchronize()
-    ctx.profile_enable(not args.no_kernel_events, every=max(1, args.kernel_events_every))
+    # The timed region: exactly --steps iterations between barrier + synchronize on both sides, maximum over ranks.  A plain run
+    # times it once; --full runs it --repeats times and reports the MEDIAN block (per-kernel HIP events accumulate over all of them).
+    if args.full:
+        ctx.profile_enable(not args.no_kernel_events, every=max(1, args.kernel_events_every))
     p.iterations = args.steps
-    # The timed region -- exactly --steps iterations between barrier + synchronize on both sides, maximum over ranks -- is
-    # run --repeats times; the MEDIAN block is the one reported (per-kernel HIP events accumulate over all of them).
     blocks = []
-    for _ in range(max(1, args.repeats)):
+    for _ in range(max(1, args.repeats) if args.full else 1):
         blocks.append(ranks.timed(lambda: ctx.demons_execute(fixed, moving, geom, p, field, want_stats=False), torch.cuda.synchronize))
     order = sorted(range(len(blocks)), key=lambda i: blocks[i][0])
     dt, per_rank, balance = blocks[order[len(order) // 2]]
+    ms_per_step = dt * 1e3 / args.steps
     repeats = {"n": len(blocks), "ms_per_step_min": blocks[order[0]][0] * 1e3 / args.steps,
-               "ms_per_step_median": dt * 1e3 / args.steps, "ms_per_step_max": blocks[order[-1]][0] * 1e3 / args.steps,
+               "ms_per_step_median": ms_per_step, "ms_per_step_max": blocks[order[-1]][0] * 1e3 / args.steps,
                "reported": "median"}
-    prof = ctx.profile_read()
-    ctx.profile_enable(False)
-    # What an EMPTY bracket reads on this stream: kernels[*].avg_ms are event-to-event times, so each carries this much beyond
-    # the kernel's own duration (which is what rocprofv3 reports) -- that is why they can add up to more than ms_per_step.
-    pair_ms = []
-    for _ in range(64):
-        ea, eb = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        ea.record()
-        eb.record()
-        eb.synchronize()
-        pair_ms.append(ea.elapsed_time(eb))
-    event_pair_ms = sorted(pair_ms)[len(pair_ms) // 2]
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, field)
+    if args.full:
+        prof = ctx.profile_read()
+        ctx.profile_enable(False)
+        # What an EMPTY bracket reads on this stream: kernels[*].avg_ms are event-to-event times, so each carries this much beyond
+        # the kernel's own duration (which is what rocprofv3 reports) -- that is why they can add up to more than ms_per_step.
+        pair_ms = []
+        for _ in range(64):
+            ea, eb = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            ea.record()
+            eb.record()
+            eb.synchronize()
+            pair_ms.append(ea.elapsed_time(eb))
+        event_pair_ms = sorted(pair_ms)[len(pair_ms) // 2]
 
     out = None
     if rank == 0:
-        kernels = {}
-        for name, (launches, total_ms) in prof.items():
-            if launches == 0:
-                continue
-            avg_ms = total_ms / launches
-            cb, kb = COMPULSORY_BYTES.get(name), CONTRACT_BYTES.get(name)
-            kernels[name] = {"launches": launches, "avg_ms": avg_ms,
-                             "compulsory_bytes_per_voxel": cb,
-                             "compulsory_GBps": (cb * nvox / (avg_ms * 1e-3) / 1e9) if cb else None,
-                             "frac_of_peak": (cb * nvox / (avg_ms * 1e-3) / 1e9 / HBM_PEAK_GBS) if cb else None,
-                             "contract_bytes_per_voxel": kb,
-                             "contract_GBps": (kb * nvox / (avg_ms * 1e-3) / 1e9) if kb else None}
-        dom = max(kernels, key=lambda k: kernels[k]["avg_ms"] * kernels[k]["launches"]) if kernels else None
-        # Measured HBM-side traffic of the same kernels: rocprofv3 --pmc passes of THIS command (tools/gpu_pmc2.sh ->
-        # profiles/round2_pmc.json, which names the commit and the raw counter file it was reduced from; FETCH_SIZE
-        # calibrated as MI355X_MICROARCH.md prescribes).  Counters cannot be read inside an untraced run, so the figure
-        # is attached only when the committed capture is of this size and these kernels.
-        pmc = load_pmc(nx, ny, nz)
-        if pmc:
-            for name, k in kernels.items():
-                tb = pmc.get("hbm_bytes_per_launch", {}).get(name)
-                if tb:
-                    k["traffic_bytes_per_voxel"] = tb / nvox
-                    k["traffic_GBps"] = tb / (k["avg_ms"] * 1e-3) / 1e9
-        roofline = None
-        if dom and kernels[dom]["compulsory_GBps"]:
-            a = kernels[dom]["compulsory_GBps"]
-            traffic = pmc.get("hbm_bytes_per_launch", {}).get(dom) if pmc else None
-            roofline = {"bound": "hbm", "kernel": dom, "achieved": a, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                        "frac": a / HBM_PEAK_GBS, "traffic": traffic,
-                        "traffic_source": ({"file": pmc.get("_file"), "commit": pmc.get("commit"), "raw": pmc.get("raw"),
-                                            "kernel_source_sha16": pmc.get("kernel_source_sha16")} if traffic else
-                                           {"note": "no committed PMC capture of these kernel sources (sha %s)" % kernel_source_sha16()}),
-                        "bytes_model": "compulsory (inputs once + outputs once of the schedule that runs)",
-                        "algorithmic_bytes_per_launch": kernels[dom]["compulsory_bytes_per_voxel"] * nvox,
-                        "avg_launch_ms": kernels[dom]["avg_ms"],
-                        "contract_model": {"bytes_per_voxel": kernels[dom]["contract_bytes_per_voxel"],
-                                           "GBps": kernels[dom]["contract_GBps"],
-                                           "note": "SURVEY 8(d) counts separable passes the fused kernel does not perform; "
-                                                   "not a bandwidth"}}
-        ms_per_step = dt * 1e3 / args.steps
-        fused_run = any(k.startswith("k_fused") for k in kernels)
-        iter_bytes = COMPULSORY_BYTES_ITER_FUSED if fused_run else CONTRACT_BYTES_ITER
-        iter_gbps = iter_bytes * nvox / (ms_per_step * 1e-3) / 1e9
         out = {
             "metric": "Mvoxels/s per demons iter, 512x512x256 fp32",
             "value": world * nvox * args.steps / dt / 1e6,
@@ -563,23 +630,13 @@ def main():
                                    f"schedule {args.variant}", "parallelism": f"1 atlas-to-target registration per GPU x{world}"},
             "ranks": balance,
             "repeats": repeats,
-            # HIP events bracket every K-th launch of each kernel inside the timed region (kernels[*].launches = bracketed launches)
-            "kernel_events_every": (None if args.no_kernel_events else max(1, args.kernel_events_every)),
-            "kernel_event_pair_ms": event_pair_ms,
-            "kernel_events_note": "kernels[*].avg_ms (and roofline.avg_launch_ms) are HIP event-to-event times on the launch stream: each "
-                                  "includes the bracket's own cost (kernel_event_pair_ms: an empty bracket on this stream) and the lost "
-                                  "back-to-back overlap, so they are upper bounds of the kernel durations rocprofv3 reports and may sum to "
-                                  "more than ms_per_step; roofline.frac is therefore conservative",
-            "roofline": roofline,
-            "roofline_iteration": {"achieved": iter_gbps, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": iter_gbps / HBM_PEAK_GBS,
-                                   "compulsory_bytes_per_voxel": iter_bytes,
-                                   "contract_bytes_per_voxel": CONTRACT_BYTES_ITER,
-                                   "contract_model_GBps": CONTRACT_BYTES_ITER * nvox / (ms_per_step * 1e-3) / 1e9},
-            "kernels": kernels,
+            "full": args.full,
         }
+        if args.full:
+            out.update(kernel_report(prof, event_pair_ms, args, (nx, ny, nz), ms_per_step))
 
     # one whole config-2 registration (3 levels, 10/10/10) through the drop-in API, for the record
-    if not args.no_registration and world == 1 and (nx, ny, nz) == (512, 512, 256):
+    if args.full and not args.no_registration and world == 1 and (nx, ny, nz) == (512, 512, 256):
         try:
             from platipy_amd.image import Image
             from platipy_amd.registration.deformable import fast_symmetric_forces_demons_registration as reg
@@ -594,7 +651,7 @@ def main():
         except Exception as e:  # keep the headline line even if the optional leg fails
             out["registration_s"] = f"failed: {e!r}"
 
-    if not args.no_atlas and (nx, ny, nz) == (512, 512, 256):
+    if args.full and not args.no_atlas and (nx, ny, nz) == (512, 512, 256):
         # The multi-atlas legs are extras around the headline metric.  At N > 1 a rank that fails before a collective
         # would leave the others waiting: a watchdog prints the line without the unfinished leg and ends the process.
         watchdog = None
@@ -663,7 +720,7 @@ def main():
     else:
         ranks.count()
     if rank == 0:
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(fixed, moving, spacing)
         print(json.dumps(out))
     ranks.close()

@@ -36,11 +36,12 @@ def test_multiatlas_exchanges_and_bench_ranks_over_rccl_world_1(gpu_backend):
 
 @pytest.mark.gpu
 def test_bench_line_under_torchrun_with_one_rank(gpu_backend, tmp_path):
-    """`torchrun --nproc-per-node 1 bench.py --gpus 1`: WORLD_SIZE=1 makes bench.Ranks open the RCCL communicator
-    (device_id=cuda:0); the line must report rccl_ranks == 1 and the metric of the plain run."""
+    """`torchrun --nproc-per-node 1 bench.py --gpus 1 --full`: WORLD_SIZE=1 makes bench.Ranks open the RCCL communicator
+    (device_id=cuda:0); the line must report rccl_ranks == 1 and the metric of a run started without a launcher."""
     port = 35500 + (os.getpid() % 2000)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1",
-           "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "10", "--warmup", "2", "--repeats", "2", "--no-cpu-baseline", "--no-registration"]
+           "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "10", "--warmup", "2", "--full", "--repeats", "2", "--no-cpu-baseline",
+           "--no-registration"]
     env = _env(port)
     p = subprocess.run(cmd, env=env, cwd=ROOT, capture_output=True, text=True, timeout=900)
     assert p.returncode == 0, p.stdout[-3000:] + "\n" + p.stderr[-3000:]

@@ -17,7 +17,7 @@ ROUND=${1:-5}
 OUT=gpurun_out/r${ROUND}final
 mkdir -p $OUT
 COMMIT=${2:-unknown}
-BENCH="python bench.py --steps 20 --warmup 3 --no-registration --no-atlas --no-cpu-baseline"
+BENCH="python bench.py --steps 20 --warmup 3 --full --no-registration --no-atlas --no-cpu-baseline"
 echo "== pytest -m gpu"; PP_STATS_DIR=$OUT/parity_stats timeout 1500 python -m pytest tests -m gpu -q 2>&1 | tail -4 | tee $OUT/pytest_gpu.log
 echo "== smoke"; timeout 300 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -1 | tee $OUT/smoke.log
 for set in "FETCH_SIZE" "WRITE_SIZE" "TCC_HIT_sum TCC_MISS_sum" "SQ_WAVES SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_WAIT_INST_LDS SQ_INSTS_VALU SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_WAIT_ANY" "SQ_INSTS_LDS SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_INSTS_SALU SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS"; do
@@ -32,10 +32,10 @@ cat $OUT/pmc.json
 # run's capture there first, so that the committed line and the committed capture come from the same build
 cp $OUT/pmc.json profiles/round${ROUND}_pmc.json
 cp $OUT/pmc_counters.md profiles/round${ROUND}_pmc_counters.md
-python bench.py > $OUT/bench.json 2> $OUT/bench.err
+python bench.py --full > $OUT/bench.json 2> $OUT/bench.err
 tail -c 600 $OUT/bench.json
 echo "== bench.py --gpus 1 under torchrun (one-rank RCCL communicator)"
-timeout 900 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29611 bench.py --gpus 1 --no-cpu-baseline > $OUT/bench_torchrun1.json 2> $OUT/bench_torchrun1.err
+timeout 900 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29611 bench.py --gpus 1 --full --no-cpu-baseline > $OUT/bench_torchrun1.json 2> $OUT/bench_torchrun1.err
 tail -c 400 $OUT/bench_torchrun1.json
 ( cd /tmp && rocprofv3 --kernel-trace --stats --output-format csv -d $OLDPWD/$OUT/trace -o trace -- bash -c "cd $OLDPWD && $BENCH" > $OLDPWD/$OUT/bench_under_rocprof.json 2> $OLDPWD/$OUT/trace.err )
 python - <<PY > $OUT/kernel_stats.md
