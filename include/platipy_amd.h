@@ -256,6 +256,34 @@ int pp_binary_morph_ball_u8(pp_ctx* ctx, const uint8_t* in, const int size[3], c
  * zmax}; an empty volume gives xmin > xmax.  dtype = PP_DTYPE_U8 or PP_DTYPE_F32.  Synchronises. */
 int pp_bounding_box(pp_ctx* ctx, const void* data, int dtype, const int size[3], int box[6]);
 
+/* ---- STAPLE ------------------------------------------------------------------------ */
+#define PP_STAPLE_MAX_RATERS 64
+enum { PP_STAPLE_FOREGROUND = 0, PP_STAPLE_BINARY_THRESHOLD = 1 };
+typedef struct {
+  int foreground_test;          /* PP_STAPLE_FOREGROUND: fg - 1e-10 < v < fg + 1e-10 (sitk.STAPLE's own test);
+                                   PP_STAPLE_BINARY_THRESHOLD: 0.5 <= v <= 255 (sitk.BinaryThreshold(lowerThreshold=0.5)
+                                   first, label/fusion.py:218); both compared in double                        */
+  int rescale;                  /* 1: RescaleIntensity(W, 0, 1), then values outside [threshold_lower, 1] -> 0  */
+  double foreground_value;
+  double confidence_weight;
+  uint64_t maximum_iterations;  /* UINT64_MAX: until convergence                                                */
+  double threshold_lower;       /* with rescale; -inf skips the threshold                                       */
+} pp_staple_params;
+typedef struct {
+  double sensitivity[PP_STAPLE_MAX_RATERS];   /* p_j of the last M step (NaN when degenerate)                   */
+  double specificity[PP_STAPLE_MAX_RATERS];   /* q_j                                                            */
+  uint64_t elapsed_iterations;
+  int64_t n_zero, n_one, n_mixed;             /* voxels no rater / every rater / some raters mark                */
+  int degenerate;                             /* no rater marks anything or every rater marks everything: W is the
+                                                 initial estimate (all 0 or all 1), no EM step ran                */
+  int reserved;
+} pp_staple_result;
+/* sitk.STAPLE(labels, confidence_weight, foreground_value) (label/fusion.py:223; itk::STAPLEImageFilter's EM with ITK's
+ * 1e-14 stopping test, plus a stop on a floating-point 2-cycle of (p, q)).  labels: host array of `nraters` (1..64)
+ * device pointers to n voxels each, dtype PP_DTYPE_U8 or PP_DTYPE_F32.  w: n fp64 voxels out.  Synchronises. */
+int pp_staple_fuse(pp_ctx* ctx, const void* const* labels, int dtype, int nraters, size_t n,
+                   const pp_staple_params* params, double* w, pp_staple_result* result);
+
 /* ---- iterative atlas removal ------------------------------------------------------- */
 /* sitk.LabelContour(mask) with face connectivity (label/projection.py:85): object voxels that have a face
  * neighbour of a different value. */

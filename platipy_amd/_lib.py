@@ -88,6 +88,21 @@ class ProfileEntry(C.Structure):
     _fields_ = [("name", C.c_char * 48), ("launches", C.c_int), ("total_ms", C.c_double)]
 
 
+STAPLE_MAX_RATERS = 64
+STAPLE_FOREGROUND, STAPLE_BINARY_THRESHOLD = 0, 1
+
+
+class StapleParams(C.Structure):    # pp_staple_params
+    _fields_ = [("foreground_test", C.c_int), ("rescale", C.c_int), ("foreground_value", C.c_double),
+                ("confidence_weight", C.c_double), ("maximum_iterations", C.c_uint64), ("threshold_lower", C.c_double)]
+
+
+class StapleResult(C.Structure):    # pp_staple_result
+    _fields_ = [("sensitivity", C.c_double * STAPLE_MAX_RATERS), ("specificity", C.c_double * STAPLE_MAX_RATERS),
+                ("elapsed_iterations", C.c_uint64), ("n_zero", C.c_int64), ("n_one", C.c_int64), ("n_mixed", C.c_int64),
+                ("degenerate", C.c_int), ("reserved", C.c_int)]
+
+
 class PlatipyAmdError(RuntimeError):
     pass
 
@@ -136,6 +151,8 @@ _SIGNATURES = {
     "pp_fillhole_largest_component_u8": (C.c_int, [_P, _P, C.POINTER(C.c_int), C.c_int, _P, C.POINTER(C.c_int64)]),
     "pp_binary_morph_ball_u8": (C.c_int, [_P, _P, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int, _P]),
     "pp_bounding_box": (C.c_int, [_P, _P, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "pp_staple_fuse": (C.c_int, [_P, C.POINTER(_P), C.c_int, C.c_int, C.c_size_t, C.POINTER(StapleParams), _P,
+                                 C.POINTER(StapleResult)]),
     "pp_label_contour_u8": (C.c_int, [_P, _P, C.POINTER(C.c_int), _P]),
     "pp_distance_map_f32": (C.c_int, [_P, _P, C.POINTER(Geom), C.c_int, C.c_int, _P]),
     "pp_meansq_affine_f32": (C.c_int, [_P, _P, C.POINTER(C.c_int), _P, C.POINTER(C.c_int), C.POINTER(C.c_double),
@@ -442,6 +459,18 @@ class Context:
         box = (C.c_int * 6)()
         self._chk(self.lib.pp_bounding_box(self.h, ptr(data), 1 if is_float else 0, _i3(size), box), "pp_bounding_box")
         return [box[i] for i in range(6)]
+
+    def staple(self, labels, is_float, n, out, foreground_test, foreground_value=1.0, confidence_weight=1.0,
+               maximum_iterations=None, rescale=False, threshold_lower=float("-inf")):
+        """pp_staple_fuse over `labels` (uint8, or float32 when is_float) -> StapleResult; W (fp64) into `out`.
+        maximum_iterations None = until convergence."""
+        prm = StapleParams(int(foreground_test), int(bool(rescale)), float(foreground_value), float(confidence_weight),
+                           (1 << 64) - 1 if maximum_iterations is None else int(maximum_iterations), float(threshold_lower))
+        ptrs = (_P * len(labels))(*[ptr(x) for x in labels])
+        res = StapleResult()
+        self._chk(self.lib.pp_staple_fuse(self.h, ptrs, 1 if is_float else 0, len(labels), int(n), C.byref(prm), ptr(out),
+                                          C.byref(res)), "pp_staple_fuse")
+        return res
 
     def label_contour(self, mask, size, out):
         self._chk(self.lib.pp_label_contour_u8(self.h, ptr(mask), _i3(size), ptr(out)), "pp_label_contour_u8")

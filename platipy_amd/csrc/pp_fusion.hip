@@ -1938,3 +1938,6 @@ int pp_linear_set_sample_jitter(pp_ctx* ctx, const float* jitter, size_t nsample
 }
 
 }  // extern "C"
+
+// STAPLE (label/fusion.py:223): kernels in the same unnamed namespace, pp_staple_fuse
+#include "pp_staple.h"

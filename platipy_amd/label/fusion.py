@@ -1,13 +1,41 @@
-"""Drop-in for platipy/imaging/label/fusion.py: compute_weight_map (:56-202), combine_labels (:239-292)
-and process_probability_image (:295-328) on volumes resident in HBM.
+"""Drop-in for platipy/imaging/label/fusion.py: compute_weight_map (:56-202), combine_labels (:239-292),
+combine_labels_staple (:205-236) and process_probability_image (:295-328) on volumes resident in HBM.
 
 Out of scope, as in SURVEY 8(a8): vote_type="patch_correlation" (a Python per-patch loop in the
-reference, :119-128), combine_labels_staple and mutual_information raise NotImplementedError.
+reference, :119-128) and mutual_information raise NotImplementedError.
+
+STAPLE (`staple`, sitk.STAPLE / itk::STAPLEImageFilter, Warfield et al. 2004), as implemented by pp_staple_fuse.
+With R raters, N voxels and D_ij = 1 iff fg - 1e-10 < v_ij < fg + 1e-10 (compared in double):
+  1. W_i = (sum_j D_ij) / R;  g = (sum_i W_i / N) * confidence_weight, with sum_i W_i formed exactly as
+     (sum of the popcounts) / R.  g is not updated afterwards.
+  2. last_p_j = last_q_j = -10.
+  3. for iter = 0, 1, ... while iter < maximum_iterations:
+       M step  p_j = sum_i W_i D_ij / sum_i W_i,  q_j = sum_i (1 - W_i)(1 - D_ij) / sum_i (1 - W_i)  (both denominators summed)
+       E step  a_i = prod_j (D_ij ? p_j : 1 - p_j),  b_i = prod_j (D_ij ? 1 - q_j : q_j)  (from 1.0, in rater order),
+               W_i = g a_i / (g a_i + (1 - g) b_i)
+       stop when |last_p_j - p_j| < 1e-14 and |last_q_j - q_j| < 1e-14 for every j, else last = current.
+  4. elapsed_iterations = iter at the break (maximum_iterations if it never breaks); sensitivity = p, specificity = q.
+Every quantity is a function of a voxel's rater bits, so the GPU packs them into one 64-bit key per voxel, runs the EM
+loop over the compacted keys of the voxels some but not all raters mark, and adds the two uniform classes analytically
+(hence at most 64 raters).  The sums are fixed-order trees: repeated runs are bit-identical.
+Two deliberate deviations from ITK, both where ITK gives NaN or never stops:
+  * degenerate input -- sum W or sum (1 - W) is 0 at the first M step (no rater marks anything, or every rater marks
+    everything): EM is skipped, W = W_initial (all 0 or all 1), p = q = NaN, and a RuntimeWarning is issued.  ITK
+    returns an all-NaN image.
+  * a floating-point 2-cycle -- (p, q) equal, bit for bit, the iterate of two steps earlier -- also stops the loop.
+    ITK would iterate forever.
+combine_labels_staple binarises each label as sitk.BinaryThreshold(label, lowerThreshold=0.5) does, 0.5 <= v <= 255
+(BinaryThreshold's default upper bound), compared in double as pp_binary_threshold_f32 compares; whether SimpleITK first
+casts 0.5 to an integer pixel type is not pinned.
 """
+import math
+import warnings
+from collections import namedtuple
+
 import numpy as np
 import torch
 
-from .. import runtime
+from .. import _lib, runtime
 from ..image import Image, as_image
 
 DEFAULT_VOTE_PARAMS = {
@@ -171,8 +199,66 @@ def _process_probability_image(probability_image, threshold):
     return probability_image.like(out)
 
 
+StapleResult = namedtuple("StapleResult", "image sensitivity specificity elapsed_iterations")
+
+
+def _staple_inputs(labels):
+    """Validated rater tensors: bool / uint8 as bytes, anything else through fp32 (as label_tensor reads labels)."""
+    labels = [as_image(x) for x in labels]
+    if not labels:
+        raise ValueError("STAPLE needs at least one rater")
+    if len(labels) > _lib.STAPLE_MAX_RATERS:
+        raise ValueError(f"STAPLE takes at most {_lib.STAPLE_MAX_RATERS} raters, got {len(labels)}")
+    ref = labels[0]
+    for x in labels:
+        if x.is_vector:
+            raise ValueError("STAPLE labels are scalar images")
+        if not ref.same_grid(x):
+            raise ValueError("STAPLE labels must share one grid (size, spacing, origin, direction)")
+        if x.device != ref.device:
+            raise ValueError(f"STAPLE labels are on different devices ({ref.device}, {x.device})")
+    is_float = any(x.tensor.dtype not in (torch.uint8, torch.bool) for x in labels)
+    ts = [label_tensor(x) for x in labels]
+    if is_float:
+        ts = [t.to(torch.float32).contiguous() for t in ts]
+    return ref, ts, is_float
+
+
+def _staple_run(labels, foreground_test, foreground_value=1.0, confidence_weight=1.0, maximum_iterations=None, rescale=False,
+                threshold_lower=-math.inf):
+    ref, ts, is_float = _staple_inputs(labels)
+    ctx = runtime.context(ref.device)
+    out = torch.empty(ts[0].shape, dtype=torch.float64, device=ts[0].device)
+    res = ctx.staple(ts, is_float, out.numel(), out, foreground_test, foreground_value, confidence_weight, maximum_iterations,
+                     rescale, threshold_lower)
+    if res.degenerate:
+        warnings.warn("STAPLE: no rater marks any voxel, or every rater marks every voxel; returning the initial estimate "
+                      "with NaN sensitivity and specificity", RuntimeWarning, stacklevel=3)
+    r = len(ts)
+    return StapleResult(ref.like(out), [res.sensitivity[j] for j in range(r)], [res.specificity[j] for j in range(r)],
+                        int(res.elapsed_iterations))
+
+
+def staple(labels, confidence_weight=1.0, foreground_value=1.0, maximum_iterations=None):
+    """sitk.STAPLE(labels, confidenceWeight, foregroundValue, maximumIterations) on the GPU (see the module notes).
+    labels: 1..64 Images on one grid and device.  maximum_iterations None = until convergence (ITK: 2^32 - 1).
+    -> StapleResult(image = float64 W, sensitivity, specificity (lists of float, one per rater), elapsed_iterations)."""
+    return _staple_run(labels, _lib.STAPLE_FOREGROUND, foreground_value, confidence_weight, maximum_iterations)
+
+
 def combine_labels_staple(label_list_dict, threshold=1e-4):
-    raise NotImplementedError("STAPLE is outside the MI355X hot path (SURVEY 8 a8)")
+    """Combine labels using STAPLE (reference fusion.py:205-236).  label_list_dict[atlas][structure] is a label Image;
+    every atlas must hold every structure (KeyError otherwise).  Per structure: BinaryThreshold(lowerThreshold=0.5),
+    STAPLE with its defaults, RescaleIntensity(0, 1) and, if `threshold`, Threshold(threshold, 1, outside 0) -- fused in
+    the last pass.  -> {structure name (sorted, np.unique): float64 Image on the first atlas's grid}."""
+    structure_name_list = [list(i.keys()) for i in label_list_dict.values()]
+    structure_name_list = np.unique([item for sublist in structure_name_list for item in sublist])
+    combined_label_dict = {}
+    for structure_name in structure_name_list:
+        labels = [label_list_dict[i][structure_name] for i in label_list_dict]
+        combined_label_dict[structure_name] = _staple_run(labels, _lib.STAPLE_BINARY_THRESHOLD, rescale=True,
+                                                          threshold_lower=threshold if threshold else -math.inf).image
+    return combined_label_dict
 
 
 def mutual_information(arr_a, arr_b, bins=64):
