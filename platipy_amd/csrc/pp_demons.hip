@@ -312,13 +312,12 @@ constexpr int TILE_OUT = 1024;
 template <int SH> struct tile_shape;
 template <> struct tile_shape<0> { static constexpr int TX = 64, TY = 16; };
 template <> struct tile_shape<1> { static constexpr int TX = 32, TY = 32; };
-// OPT = outputs per thread along x (4: 256 threads, float4 rows; 2: 512 threads, float2 rows -- half the
-// registers per thread, twice the waves per CU for the same LDS tile).
-template <int R, int OPT, int SH>
+// Two outputs per thread along x: 512 threads, float2 rows.
+template <int R, int SH>
 struct fused_geom {
   static constexpr int TX = tile_shape<SH>::TX, TY = tile_shape<SH>::TY;
-  static constexpr int NTH = TX * TY / OPT;       // threads per block
-  static constexpr int LX = TX / OPT;             // threads along x
+  static constexpr int NTH = TX * TY / 2;         // threads per block
+  static constexpr int LX = TX / 2;               // threads along x
   static constexpr int UW = TX + 2 * R;           // smoothing-input tile width  (x from tx0 - R)
   static constexpr int UH = TY + 2 * R;           // smoothing-input tile height (y from ty0 - R)
   static constexpr int UWP = (UW + 3) / 4 * 4;    // row pitch, keeps rows 16-B aligned
@@ -326,14 +325,11 @@ struct fused_geom {
   static constexpr int KU = (NU + NTH - 1) / NTH;   // of which one thread owns at most KU
   static constexpr int MW = UW + 2;               // image tile (1 more voxel each side for gradients)
   static constexpr int MH = UH + 2;
-  // Row pitch of the packed image tile (float2).  OPT == 2 (the 512-thread kernels): padded to UW + 32, so that the ESM pass's
+  // Row pitch of the packed image tile (float2), padded to UW + 32 so that the ESM pass's
   // ds_read_b64 of a wave -- 64 consecutive update voxels, which wrap from one 68-voxel row into the next -- still touches 64
   // distinct banks after the wrap (2 (MWP - UW) = 64 dwords: the same bank phase); unpadded, every wrapped wave-read hit two
   // banks twice (+39 % cycles on kernel A's most frequent LDS read, MI355X_MICROARCH.md's LDS table).
-#ifndef PP_A_MWP_PAD
-#define PP_A_MWP_PAD 1
-#endif
-  static constexpr int MWP = (PP_A_MWP_PAD != 0 && OPT == 2) ? UW + 32 : MW;
+  static constexpr int MWP = UW + 32;
   static constexpr int NB = MW * MH - UW * UH;    // border ring elements
   static constexpr int XI = UH * (TX / 4);        // x-pass work items per component
   // LDS carve (floats): region 1 holds the two image tiles during the force phase and is reused for
@@ -349,10 +345,10 @@ struct fused_geom {
 };
 
 // x pass: item (row uy, group cx) reads 4 + 2R inputs of `us` and writes 4 outputs to `xs`.
-template <int R, int OPT, int SH>
+template <int R, int SH>
 __device__ __forceinline__ void fused_xpass(const float* __restrict__ us /*[3][UH][UWP]*/,
                                             float* __restrict__ xs /*[3][UH][TX]*/, const pp_taps_small& wx) {
-  using G = fused_geom<R, OPT, SH>;
+  using G = fused_geom<R, SH>;
   constexpr int TX = G::TX;
   for (int it = threadIdx.x; it < 3 * G::XI; it += G::NTH) {
     const int c = it / G::XI;
@@ -366,7 +362,7 @@ __device__ __forceinline__ void fused_xpass(const float* __restrict__ us /*[3][U
       const float4 v = *reinterpret_cast<const float4*>(src + 4 * q);
       in[4 * q + 0] = v.x; in[4 * q + 1] = v.y; in[4 * q + 2] = v.z; in[4 * q + 3] = v.w;
     }
-    if ((4 + 2 * R) % 4 == 2) {
+    if constexpr ((4 + 2 * R) % 4 == 2) {
       const float2 v = *reinterpret_cast<const float2*>(src + (4 + 2 * R) / 4 * 4);
       in[(4 + 2 * R) / 4 * 4 + 0] = v.x;
       in[(4 + 2 * R) / 4 * 4 + 1] = v.y;
@@ -383,41 +379,32 @@ __device__ __forceinline__ void fused_xpass(const float* __restrict__ us /*[3][U
   }
 }
 
-// y pass for this thread's OPT outputs of component c.
-template <int R, int OPT, int SH>
+// y pass for this thread's two outputs of component c.
+template <int R, int SH>
 __device__ __forceinline__ void fused_ypass(const float* __restrict__ xs, int c, int cx, int cy, const pp_taps_small& wy,
-                                            float v[OPT]) {
-  using G = fused_geom<R, OPT, SH>;
+                                            float v[2]) {
+  using G = fused_geom<R, SH>;
   constexpr int TX = G::TX;
 #pragma unroll
-  for (int j = 0; j < OPT; ++j) v[j] = 0.0f;
+  for (int j = 0; j < 2; ++j) v[j] = 0.0f;
 #pragma unroll
   for (int k = 0; k < 2 * R + 1; ++k) {
-    const float* p = xs + (c * G::UH + cy + k) * TX + OPT * cx;
-    if (OPT == 4) {
-      const float4 a = *reinterpret_cast<const float4*>(p);
-      const float w = wy.h[k < R ? R - k : k - R];
-      v[0] = fmaf(w, a.x, v[0]);
-      v[1] = fmaf(w, a.y, v[1]);
-      v[2] = fmaf(w, a.z, v[2]);
-      v[3] = fmaf(w, a.w, v[3]);
-    } else {
-      const float2 a = *reinterpret_cast<const float2*>(p);
-      const float w = wy.h[k < R ? R - k : k - R];
-      v[0] = fmaf(w, a.x, v[0]);
-      v[1] = fmaf(w, a.y, v[1]);
-    }
+    const float* p = xs + (c * G::UH + cy + k) * TX + 2 * cx;
+    const float2 a = *reinterpret_cast<const float2*>(p);
+    const float w = wy.h[k < R ? R - k : k - R];
+    v[0] = fmaf(w, a.x, v[0]);
+    v[1] = fmaf(w, a.y, v[1]);
   }
 }
 
-template <int R, int OPT>
+template <int R>
 struct zring {
-  float r[3][OPT][2 * R + 1];
-  __device__ __forceinline__ void push(const float v[3][OPT]) {
+  float r[3][2][2 * R + 1];
+  __device__ __forceinline__ void push(const float v[3][2]) {
 #pragma unroll
     for (int c = 0; c < 3; ++c)
 #pragma unroll
-      for (int j = 0; j < OPT; ++j) {
+      for (int j = 0; j < 2; ++j) {
 #pragma unroll
         for (int k = 0; k < 2 * R; ++k) r[c][j][k] = r[c][j][k + 1];
         r[c][j][2 * R] = v[c][j];
@@ -446,36 +433,33 @@ struct fused_args {
   // rows are not whole 16-byte quads into padded rows once: strips are then 16-byte aligned and pairs 8-byte aligned for any
   // row length, and the MASK instances (which need pairs) serve odd row lengths too.  Padding is written, never read as data.
   int px;
-  // generation 2, PP_SOFTSYNC builds: progress words of this kernel's launch (8 XCDs x 64 resident blocks), the other kernel's
-  // set (cleared by this launch) and the allowed lead in plane steps (0: publish only)
+  // generation 2, MASK instances: progress words of this kernel's launch (8 XCDs x 64 resident blocks) for the pair priority,
+  // and the other kernel's set (cleared by this launch)
   unsigned* sync;
   unsigned* sync_other;
-  int sync_lag;
+  // Unused.  It keeps the taps below at their offsets in the kernel arguments: moved 4 bytes, they are paired into scalar
+  // registers differently and the generated code of the generation-2 kernels changes throughout.
+  int unused_slot;
   pp_taps_small wx, wy, wz;
 };
 
 // Tile of this block (see the grid note above); false for the few surplus blocks of the last XCD run.  `region`: which
 // of the two tile regions of a mixed launch the caller's tile shape belongs to (0 when there is one shape).
-// PP_PAIR_MIX (round 5): tile columns differ systematically in how long a block takes on them (x-border tiles re-read their
+// Pair mix: tile columns differ systematically in how long a block takes on them (x-border tiles re-read their
 // clamped halo from lines they already hold; at 512 x 512 x 256 kernel A's columns 0, 3, 4, 7 end ~18 us and kernel B's
 // columns 0, 7 ~33 us before the others), and the dispatcher gives a CU the XCD run's blocks j and j + 32 -- the SAME column
 // twice when the run is a whole number of tile rows.  So the second block of a CU takes its x-NEIGHBOUR's tile instead
 // (rank ^ 1, where both ranks lie in the second half of this XCD's run, in the 64 x 16 region and in one tile row: a bijection
 // on the tiles): every CU then hosts a slow and a fast column, and the pair priority (pp_demons_fused2.h) levels them.
 // Measured with it: an XCD's blocks end within 11 us (A) / 16 us (B) of each other instead of 27 / 40, iteration -2.0 .. -2.8 %.
-#ifndef PP_PAIR_MIX
-#define PP_PAIR_MIX 1
-#endif
 __device__ __forceinline__ unsigned fused_rank(const fused_args& a) {
   const unsigned b = blockIdx.x;
   const unsigned first = (b & 7u) * (unsigned)a.per_xcd, j = b >> 3;
   unsigned rank = first + j;
-#if PP_PAIR_MIX
   if (j >= 32u) {
     const unsigned lo = rank & ~1u, hi = lo | 1u, n1 = (unsigned)a.gx * a.gy * a.gz;
     if (lo >= first + 32u && hi < first + (unsigned)a.per_xcd && hi < n1 && (hi % (unsigned)a.gx) != 0u) rank ^= 1u;
   }
-#endif
   return rank;
 }
 __device__ __forceinline__ int fused_region(const fused_args& a) {   // (surplus blocks report region 0 and fail fused_tile there)
@@ -504,37 +488,12 @@ __device__ __forceinline__ float ld_off(const float* base, unsigned byte_off) {
 // per-voxel flags packed beside the LDS slots
 constexpr unsigned F_CNT = 1u, F_XLO = 2u, F_XHI = 4u, F_YLO = 8u, F_YHI = 16u, F_VALID = 32u, F_OOV = 64u;
 
-// Measurement builds only (-DPP_TRACE, tools/kbench): shader-clock stamps of one block's waves at the barriers of the
-// plane loop, read back through pp_debug_trace_read.  Product builds compile none of it.
-#ifdef PP_TRACE
-constexpr int PP_TRACE_STEPS = 140, PP_TRACE_SLOTS = 6;
-__device__ unsigned pp_trace_buf[2][8][PP_TRACE_STEPS][PP_TRACE_SLOTS];
-#define PP_TRACE_MARK(on, kern, step, slot)                                                     \
-  do {                                                                                          \
-    if ((on) && (threadIdx.x & 63u) == 0 && (step) >= 0 && (step) < PP_TRACE_STEPS)             \
-      pp_trace_buf[kern][threadIdx.x >> 6][step][slot] = (unsigned)__builtin_amdgcn_s_memtime(); \
-  } while (0)
-#else
-#define PP_TRACE_MARK(on, kern, step, slot) \
-  do {                                      \
-  } while (0)
-#endif
-
 // ---- kernel A: ESM update + 3-D Gaussian of the update ---------------------------------
-#ifndef PP_FUSED_DEFAULT_OPT
-#define PP_FUSED_DEFAULT_OPT 2
-#endif
-#ifndef PP_A_WAVES
-#define PP_A_WAVES 1
-#endif
-#ifndef PP_B_WAVES
-#define PP_B_WAVES 1
-#endif
-template <int R, int OPT, int SH>
-__global__ void __launch_bounds__(TILE_OUT / OPT, PP_A_WAVES) k_fused_force_smooth(const float* __restrict__ F, const float* __restrict__ Mw,
+template <int R, int SH>
+__global__ void __launch_bounds__(TILE_OUT / 2, 1) k_fused_force_smooth(const float* __restrict__ F, const float* __restrict__ Mw,
                                                            float* __restrict__ Us, fused_args a, pp_esm_consts K,
                                                            double* __restrict__ partials, const int* __restrict__ halt) {
-  using G = fused_geom<R, OPT, SH>;
+  using G = fused_geom<R, SH>;
   constexpr int NTH = G::NTH, TX = G::TX, TY = G::TY;
   __shared__ __attribute__((aligned(16))) float smem[G::SMEM];
   float* const s_m = smem;                      // warped moving, current plane   (force phase)
@@ -613,8 +572,8 @@ __global__ void __launch_bounds__(TILE_OUT / OPT, PP_A_WAVES) k_fused_force_smoo
     }
   }
 
-  zring<R, OPT> ring;
-  float v[3][OPT];
+  zring<R> ring;
+  float v[3][2];
   float a_ssd = 0.0f, a_ssc = 0.0f, a_n = 0.0f;   // <= ~40 terms per thread: fp32 is exact enough, folded in fp64 below
   int zc_done = -1;
 
@@ -674,10 +633,10 @@ __global__ void __launch_bounds__(TILE_OUT / OPT, PP_A_WAVES) k_fused_force_smoo
       }
       __syncthreads();  // s_u complete; region 1 (image tiles) is dead from here
       // (3) x pass, (4) y pass
-      fused_xpass<R, OPT, SH>(s_u, s_x, a.wx);
+      fused_xpass<R, SH>(s_u, s_x, a.wx);
       __syncthreads();
 #pragma unroll
-      for (int c = 0; c < 3; ++c) fused_ypass<R, OPT, SH>(s_x, c, cx, cy, a.wy, v[c]);
+      for (int c = 0; c < 3; ++c) fused_ypass<R, SH>(s_x, c, cx, cy, a.wy, v[c]);
       // rotate the z window of the image values
 #pragma unroll
       for (int k = 0; k < G::KU; ++k) {
@@ -692,20 +651,19 @@ __global__ void __launch_bounds__(TILE_OUT / OPT, PP_A_WAVES) k_fused_force_smoo
     ring.push(v);
     const int zo = zi - R;
     if (zo >= z0 && zo <= zo_last) {
-      const int x = tx0 + OPT * cx, y = ty0 + cy;
+      const int x = tx0 + 2 * cx, y = ty0 + cy;
       if (y < d.ny && x < d.nx) {
         const size_t o = (size_t)zo * sz + (size_t)y * sy + x;
 #pragma unroll
         for (int c = 0; c < 3; ++c) {
-          float r[OPT];
+          float r[2];
 #pragma unroll
-          for (int j = 0; j < OPT; ++j) r[j] = ring.dot(c, j, a.wz);
-          if ((d.nx % OPT) == 0) {
-            if (OPT == 4) *reinterpret_cast<float4*>(Us + c * N + o) = make_float4(r[0], r[1], r[2], r[OPT - 1]);
-            else *reinterpret_cast<float2*>(Us + c * N + o) = make_float2(r[0], r[1]);
+          for (int j = 0; j < 2; ++j) r[j] = ring.dot(c, j, a.wz);
+          if ((d.nx % 2) == 0) {
+            *reinterpret_cast<float2*>(Us + c * N + o) = make_float2(r[0], r[1]);
           } else {
 #pragma unroll
-            for (int j = 0; j < OPT; ++j)
+            for (int j = 0; j < 2; ++j)
               if (x + j < d.nx) Us[c * N + o + j] = r[j];
           }
         }
@@ -723,12 +681,12 @@ __global__ void __launch_bounds__(TILE_OUT / OPT, PP_A_WAVES) k_fused_force_smoo
 }
 
 // ---- kernel B: D' = G_d * (D + U), then the next iteration's warped moving image ------
-template <int R, int OPT, int SH>
-__global__ void __launch_bounds__(TILE_OUT / OPT, PP_B_WAVES) k_fused_add_smooth_warp(const float* __restrict__ D, const float* __restrict__ Us,
+template <int R, int SH>
+__global__ void __launch_bounds__(TILE_OUT / 2, 1) k_fused_add_smooth_warp(const float* __restrict__ D, const float* __restrict__ Us,
                                                               const float* __restrict__ M, float* __restrict__ Dn,
                                                               float* __restrict__ Mw, fused_args a, pp_warp_scale sc,
                                                               const int* __restrict__ halt) {
-  using G = fused_geom<R, OPT, SH>;
+  using G = fused_geom<R, SH>;
   constexpr int NTH = G::NTH, TX = G::TX, TY = G::TY;
   __shared__ __attribute__((aligned(16))) float smem[G::SZ_X + G::SZ_U];
   float* const s_x = smem;
@@ -774,8 +732,8 @@ __global__ void __launch_bounds__(TILE_OUT / OPT, PP_B_WAVES) k_fused_add_smooth
       }
   }
 
-  zring<R, OPT> ring;
-  float v[3][OPT];
+  zring<R> ring;
+  float v[3][2];
   int zc_done = -1;
 
   for (int zi = zs; zi <= ze; ++zi) {
@@ -799,26 +757,26 @@ __global__ void __launch_bounds__(TILE_OUT / OPT, PP_B_WAVES) k_fused_add_smooth
           }
       }
       __syncthreads();
-      fused_xpass<R, OPT, SH>(s_u, s_x, a.wx);
+      fused_xpass<R, SH>(s_u, s_x, a.wx);
       __syncthreads();
 #pragma unroll
-      for (int c = 0; c < 3; ++c) fused_ypass<R, OPT, SH>(s_x, c, cx, cy, a.wy, v[c]);
+      for (int c = 0; c < 3; ++c) fused_ypass<R, SH>(s_x, c, cx, cy, a.wy, v[c]);
       zc_done = zc;
     }
     ring.push(v);
     const int zo = zi - R;
     if (zo >= z0 && zo <= zo_last) {
-      const int x = tx0 + OPT * cx, y = ty0 + cy;
+      const int x = tx0 + 2 * cx, y = ty0 + cy;
       if (y < d.ny && x < d.nx) {
         const size_t o = (size_t)zo * sz + (size_t)y * sy + x;
-        float dn[3][OPT];
+        float dn[3][2];
 #pragma unroll
         for (int c = 0; c < 3; ++c)
 #pragma unroll
-          for (int j = 0; j < OPT; ++j) dn[c][j] = ring.dot(c, j, a.wz);
-        float mw[OPT];
+          for (int j = 0; j < 2; ++j) dn[c][j] = ring.dot(c, j, a.wz);
+        float mw[2];
 #pragma unroll
-        for (int j = 0; j < OPT; ++j) {
+        for (int j = 0; j < 2; ++j) {
           int bx, by, bz;
           float fx, fy, fz;
           pp_split(x + j, dn[0][j] * sc.ix, bx, fx);
@@ -827,20 +785,13 @@ __global__ void __launch_bounds__(TILE_OUT / OPT, PP_B_WAVES) k_fused_add_smooth
           const bool inside = (x + j < d.nx) && pp_inside1(bx, fx, d.nx) && pp_inside1(by, fy, d.ny) && pp_inside1(bz, fz, d.nz);
           mw[j] = inside ? pp_trilinear(M, d.nx, d.ny, d.nz, bx, fx, by, fy, bz, fz) : FLT_MAX;
         }
-        if ((d.nx % OPT) == 0) {
-          if (OPT == 4) {
+        if ((d.nx % 2) == 0) {
 #pragma unroll
-            for (int c = 0; c < 3; ++c)
-              *reinterpret_cast<float4*>(Dn + c * N + o) = make_float4(dn[c][0], dn[c][1], dn[c][2], dn[c][OPT - 1]);
-            *reinterpret_cast<float4*>(Mw + o) = make_float4(mw[0], mw[1], mw[2], mw[OPT - 1]);
-          } else {
-#pragma unroll
-            for (int c = 0; c < 3; ++c) *reinterpret_cast<float2*>(Dn + c * N + o) = make_float2(dn[c][0], dn[c][1]);
-            *reinterpret_cast<float2*>(Mw + o) = make_float2(mw[0], mw[1]);
-          }
+          for (int c = 0; c < 3; ++c) *reinterpret_cast<float2*>(Dn + c * N + o) = make_float2(dn[c][0], dn[c][1]);
+          *reinterpret_cast<float2*>(Mw + o) = make_float2(mw[0], mw[1]);
         } else {
 #pragma unroll
-          for (int j = 0; j < OPT; ++j)
+          for (int j = 0; j < 2; ++j)
             if (x + j < d.nx) {
               Dn[o + j] = dn[0][j];
               Dn[N + o + j] = dn[1][j];
@@ -855,9 +806,7 @@ __global__ void __launch_bounds__(TILE_OUT / OPT, PP_B_WAVES) k_fused_add_smooth
 
 // z-window handling of the generation-2 kernels: plane loop unrolled 2R+1 times (window renamed) up to this radius,
 // register moves above it (the unrolled body of radius 4/5 would be 9-11 copies of ~600 instructions)
-#ifndef PP_RING_UNROLL_MAX_R
-#define PP_RING_UNROLL_MAX_R 3
-#endif
+constexpr int RING_UNROLL_MAX_R = 3;
 #include "pp_demons_fused2.h"
 #include "pp_demons_cube.h"
 
@@ -889,10 +838,8 @@ void small_taps(const pp_taps& t, int R, pp_taps_small* s) {
 
 // z-chunk length: long chunks amortise the 2R (+3 image) halo planes, but the launch should fill the
 // chip a whole number of times.  `slots` = resident blocks of the slower kernel (256 CUs x blocks/CU).
-int fused_zchunk(const pp_dims& d, int slots, int TX, int TY, double* cost_out = nullptr, char kernel = 0, int tiles_override = 0) {
-  const char* e = kernel == 'A' ? pp_env("PP_FUSED_ZCHUNK_A") : (kernel == 'B' ? pp_env("PP_FUSED_ZCHUNK_B") : nullptr);
-  if (!e) e = pp_env("PP_FUSED_ZCHUNK");
-  if (e) {
+int fused_zchunk(const pp_dims& d, int slots, int TX, int TY, double* cost_out = nullptr, int tiles_override = 0) {
+  if (const char* e = pp_env("PP_FUSED_ZCHUNK")) {
     const int v = atoi(e);
     if (v >= 1) {
       if (cost_out) *cost_out = 0.0;
@@ -936,101 +883,72 @@ int fused_shape(const pp_dims& d, int slots0, int slots1) {
   return 10 * t1 < 9 * t0 ? 1 : 0;
 }
 
-// Per-kernel dispatch on (radius, outputs per thread).  The two kernels are independent: the update is smoothed
-// with sigma_u (radius RA) and the field with sigma_d (radius RB), so each runs the narrowest template that fits.
-template <int R, int OPT, int SH>
+// Per-kernel dispatch on the radius.  The two kernels are independent: the update is smoothed with sigma_u (radius RA)
+// and the field with sigma_d (radius RB), so each runs the narrowest template that fits.
+template <int R, int SH>
 int occ_force() {
   static int cache = 0;
   if (cache) return cache;
   int a = 0;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&a, k_fused_force_smooth<R, OPT, SH>, TILE_OUT / OPT, 0) != hipSuccess) a = 2;
+  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&a, k_fused_force_smooth<R, SH>, TILE_OUT / 2, 0) != hipSuccess) a = 2;
   (void)hipGetLastError();
   return cache = (a < 1 ? 1 : a);
 }
-template <int R, int OPT, int SH>
+template <int R, int SH>
 int occ_warp() {
   static int cache = 0;
   if (cache) return cache;
   int a = 0;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&a, k_fused_add_smooth_warp<R, OPT, SH>, TILE_OUT / OPT, 0) != hipSuccess) a = 2;
+  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&a, k_fused_add_smooth_warp<R, SH>, TILE_OUT / 2, 0) != hipSuccess) a = 2;
   (void)hipGetLastError();
   return cache = (a < 1 ? 1 : a);
 }
+#define PP_BY_RADIUS(R, CALL) \
+  ((R) == 1 ? CALL(1) : ((R) == 2 ? CALL(2) : ((R) == 3 ? CALL(3) : ((R) == 4 ? CALL(4) : CALL(5)))))
 
-// PP_MINI (measurement builds, tools/kbench/mini.sh): only the radius-2, 512-thread instances exist, so the file compiles in
-// seconds while a kernel is being worked on.  Product builds never define it.
-#ifdef PP_MINI
-#define PP_BY_RADIUS(R, OPT, CALL) CALL(2, 2)
-#else
-#define PP_BY_RADIUS(R, OPT, CALL)                                                                   \
-  ((OPT) == 4 ? ((R) == 1 ? CALL(1, 4) : ((R) == 2 ? CALL(2, 4) : CALL(3, 4)))                       \
-              : ((R) == 1 ? CALL(1, 2) : ((R) == 2 ? CALL(2, 2) : ((R) == 3 ? CALL(3, 2) : ((R) == 4 ? CALL(4, 2) : CALL(5, 2))))))
-#endif
-
-// The 32 x 32 shape exists for the 512-thread layout only (OPT = 2).
-template <int R, int OPT>
+template <int R>
 int occ_force_sh(int sh) {
-  if constexpr (OPT == 2) {
-    if (sh == 1) return occ_force<R, 2, 1>();
-  }
-  return occ_force<R, OPT, 0>();
+  return sh == 1 ? occ_force<R, 1>() : occ_force<R, 0>();
 }
-template <int R, int OPT>
+template <int R>
 int occ_warp_sh(int sh) {
-  if constexpr (OPT == 2) {
-    if (sh == 1) return occ_warp<R, 2, 1>();
-  }
-  return occ_warp<R, OPT, 0>();
+  return sh == 1 ? occ_warp<R, 1>() : occ_warp<R, 0>();
 }
 
-template <int R, int OPT>
+template <int R>
 int launch_force(pp_ctx* ctx, int sh, const float* F, const float* Mw_in, float* Us, const fused_args& fu, const pp_esm_consts& K,
                  double* partials, const int* halt) {
   pp_prof_scope ps(ctx, "k_fused_force_smooth");
-  if constexpr (OPT == 2) {
-    if (sh == 1) {
-      hipLaunchKernelGGL((k_fused_force_smooth<R, 2, 1>), dim3(8u * (unsigned)fu.per_xcd), dim3(TILE_OUT / 2), 0, ctx->stream, F, Mw_in, Us,
-                         fu, K, partials, halt);
-      return PP_OK;
-    }
-  }
-  hipLaunchKernelGGL((k_fused_force_smooth<R, OPT, 0>), dim3(8u * (unsigned)fu.per_xcd), dim3(TILE_OUT / OPT), 0, ctx->stream, F, Mw_in, Us,
-                     fu, K, partials, halt);
+  if (sh == 1)
+    hipLaunchKernelGGL((k_fused_force_smooth<R, 1>), dim3(8u * (unsigned)fu.per_xcd), dim3(TILE_OUT / 2), 0, ctx->stream, F, Mw_in, Us, fu, K,
+                       partials, halt);
+  else
+    hipLaunchKernelGGL((k_fused_force_smooth<R, 0>), dim3(8u * (unsigned)fu.per_xcd), dim3(TILE_OUT / 2), 0, ctx->stream, F, Mw_in, Us, fu, K,
+                       partials, halt);
   return PP_OK;
 }
-template <int R, int OPT>
+template <int R>
 int launch_warp(pp_ctx* ctx, int sh, const float* D, const float* Us, const float* M, float* Dn, float* Mw_out, const fused_args& fd,
                 const pp_warp_scale& sc, const int* halt) {
   pp_prof_scope ps(ctx, "k_fused_add_smooth_warp");
-  if constexpr (OPT == 2) {
-    if (sh == 1) {
-      hipLaunchKernelGGL((k_fused_add_smooth_warp<R, 2, 1>), dim3(8u * (unsigned)fd.per_xcd), dim3(TILE_OUT / 2), 0, ctx->stream, D, Us, M,
-                         Dn, Mw_out, fd, sc, halt);
-      return PP_OK;
-    }
-  }
-  hipLaunchKernelGGL((k_fused_add_smooth_warp<R, OPT, 0>), dim3(8u * (unsigned)fd.per_xcd), dim3(TILE_OUT / OPT), 0, ctx->stream, D, Us, M,
-                     Dn, Mw_out, fd, sc, halt);
+  if (sh == 1)
+    hipLaunchKernelGGL((k_fused_add_smooth_warp<R, 1>), dim3(8u * (unsigned)fd.per_xcd), dim3(TILE_OUT / 2), 0, ctx->stream, D, Us, M, Dn,
+                       Mw_out, fd, sc, halt);
+  else
+    hipLaunchKernelGGL((k_fused_add_smooth_warp<R, 0>), dim3(8u * (unsigned)fd.per_xcd), dim3(TILE_OUT / 2), 0, ctx->stream, D, Us, M, Dn,
+                       Mw_out, fd, sc, halt);
   return PP_OK;
 }
 
 // ---- generation 2 (pp_demons_fused2.h): 512-thread layout only, both tile shapes; kernel A for radii 1..3, kernel B 1..4
 // (beyond that the unrolled plane loop does not fit 128 registers and the first generation is faster).  SUM: see the header.
-#ifdef PP_MINI
-#define PP_BY_RADIUS_A2(R, CALL) CALL(2)
-#define PP_BY_RADIUS_B2(R, CALL) CALL(2)
-#else
 #define PP_BY_RADIUS_A2(R, CALL) ((R) == 1 ? CALL(1) : ((R) == 2 ? CALL(2) : CALL(3)))
 #define PP_BY_RADIUS_B2(R, CALL) ((R) == 1 ? CALL(1) : ((R) == 2 ? CALL(2) : ((R) == 3 ? CALL(3) : CALL(4))))
-#endif
-#define PP_A2_KERNEL(SHV, SUMV, NTV, MASKV) k_fused2_force_smooth<R, SHV, (R <= PP_RING_UNROLL_MAX_R), SUMV, NTV, MASKV>
-#define PP_B2_KERNEL(SHV, SUMV, NTV, MASKV) k_fused2_add_smooth_warp<R, SHV, (R <= PP_RING_UNROLL_MAX_R), SUMV, NTV, MASKV>
+#define PP_A2_KERNEL(SHV, SUMV, NTV, MASKV) k_fused2_force_smooth<R, SHV, (R <= RING_UNROLL_MAX_R), SUMV, NTV, MASKV>
+#define PP_B2_KERNEL(SHV, SUMV, NTV, MASKV) k_fused2_add_smooth_warp<R, SHV, (R <= RING_UNROLL_MAX_R), SUMV, NTV, MASKV>
 // fields of >= 2^32 bytes (fused_args::big): SUM, streaming stores, branchy instances, 64-bit bases for the field arrays
-#define PP_A2_KERNEL_BIG(SHV) k_fused2_force_smooth<R, SHV, (R <= PP_RING_UNROLL_MAX_R), true, true, false, true>
-#define PP_B2_KERNEL_BIG(SHV) k_fused2_add_smooth_warp<R, SHV, (R <= PP_RING_UNROLL_MAX_R), true, true, false, true>
-#ifndef PP_MINI_MASK
-#define PP_MINI_MASK true
-#endif
+#define PP_A2_KERNEL_BIG(SHV) k_fused2_force_smooth<R, SHV, (R <= RING_UNROLL_MAX_R), true, true, false, true>
+#define PP_B2_KERNEL_BIG(SHV) k_fused2_add_smooth_warp<R, SHV, (R <= RING_UNROLL_MAX_R), true, true, false, true>
 
 template <int R>
 int occ_force2(int sh) {   // (cached: the answer depends on the kernel binary only, and the query costs ~10 us per call)
@@ -1038,13 +956,9 @@ int occ_force2(int sh) {   // (cached: the answer depends on the kernel binary o
   sh = sh < 0 ? 0 : (sh > 2 ? 2 : sh);
   if (cache[sh]) return cache[sh];
   int a = 0;
-#ifdef PP_MINI
-  const hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&a, PP_A2_KERNEL(0, true, true, PP_MINI_MASK), 512, 0);
-#else
   const hipError_t e = sh == 2 ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&a, PP_A2_KERNEL(2, true, false, true), 512, 0)
                        : sh  ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&a, PP_A2_KERNEL(1, true, false, true), 512, 0)
                              : hipOccupancyMaxActiveBlocksPerMultiprocessor(&a, PP_A2_KERNEL(0, true, false, true), 512, 0);
-#endif
   if (e != hipSuccess) a = 2;
   (void)hipGetLastError();
   return cache[sh] = (a < 1 ? 1 : a);
@@ -1055,13 +969,9 @@ int occ_warp2(int sh) {   // (cached: the answer depends on the kernel binary on
   sh = sh < 0 ? 0 : (sh > 2 ? 2 : sh);
   if (cache[sh]) return cache[sh];
   int a = 0;
-#ifdef PP_MINI
-  const hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&a, PP_B2_KERNEL(0, true, true, PP_MINI_MASK), 512, 0);
-#else
   const hipError_t e = sh == 2 ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&a, PP_B2_KERNEL(2, true, false, true), 512, 0)
                        : sh  ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&a, PP_B2_KERNEL(1, true, false, true), 512, 0)
                              : hipOccupancyMaxActiveBlocksPerMultiprocessor(&a, PP_B2_KERNEL(0, true, false, true), 512, 0);
-#endif
   if (e != hipSuccess) a = 2;
   (void)hipGetLastError();
   return cache[sh] = (a < 1 ? 1 : a);
@@ -1075,10 +985,6 @@ int launch_force2(pp_ctx* ctx, int sh, bool sum, const float* F, const float* Mw
   hipLaunchKernelGGL((PP_A2_KERNEL(SHV, SUMV, NTV, MASKV)), grid, block, 0, ctx->stream, F, Mw_in, D, Us, fu, K, partials, st, prev, nprev, max_rms)
 #define PP_GO_BIG(SHV) \
   hipLaunchKernelGGL((PP_A2_KERNEL_BIG(SHV)), grid, block, 0, ctx->stream, F, Mw_in, D, Us, fu, K, partials, st, prev, nprev, max_rms)
-#ifdef PP_MINI
-  (void)sh;
-  PP_GO(0, true, true, PP_MINI_MASK);
-#else
   if (fu.big) {
     if (sh == 2) PP_GO_BIG(2); else if (sh) PP_GO_BIG(1); else PP_GO_BIG(0);
   } else if (!sum) {   // (PP_FUSED_SUM=0, a measurement path: cached stores only)
@@ -1091,7 +997,6 @@ int launch_force2(pp_ctx* ctx, int sh, bool sum, const float* F, const float* Mw
   } else {
     if (sh == 2) PP_GO(2, true, false, false); else if (sh) PP_GO(1, true, false, false); else PP_GO(0, true, false, false);
   }
-#endif
 #undef PP_GO
 #undef PP_GO_BIG
   return PP_OK;
@@ -1103,10 +1008,6 @@ int launch_warp2(pp_ctx* ctx, int sh, bool sum, const float* D, const float* Us,
   const dim3 grid(8u * (unsigned)fd.per_xcd), block(512);
 #define PP_GO(SHV, SUMV, NTV, MASKV) hipLaunchKernelGGL((PP_B2_KERNEL(SHV, SUMV, NTV, MASKV)), grid, block, 0, ctx->stream, D, Us, M, Dn, Mw_out, fd, sc, halt)
 #define PP_GO_BIG(SHV) hipLaunchKernelGGL((PP_B2_KERNEL_BIG(SHV)), grid, block, 0, ctx->stream, D, Us, M, Dn, Mw_out, fd, sc, halt)
-#ifdef PP_MINI
-  (void)sh;
-  PP_GO(0, true, true, PP_MINI_MASK);
-#else
   if (fd.big) {
     if (sh == 2) PP_GO_BIG(2); else if (sh) PP_GO_BIG(1); else PP_GO_BIG(0);
   } else if (!sum) {
@@ -1119,7 +1020,6 @@ int launch_warp2(pp_ctx* ctx, int sh, bool sum, const float* D, const float* Us,
   } else {
     if (sh == 2) PP_GO(2, true, false, false); else if (sh) PP_GO(1, true, false, false); else PP_GO(0, true, false, false);
   }
-#endif
 #undef PP_GO
 #undef PP_GO_BIG
   return PP_OK;
@@ -1168,7 +1068,7 @@ bool fused_mix_ok(const pp_dims& d) {
   return shape_ok && (size_t)d.nx * d.ny * d.nz >= ((size_t)8 << 20);
 }
 
-void fused_grid(fused_args* f, const pp_dims& d, int occupancy, int sh, char kernel, int px = 0) {
+void fused_grid(fused_args* f, const pp_dims& d, int occupancy, int sh, int px = 0) {
   const int TX = sh == 1 ? tile_shape<1>::TX : tile_shape<0>::TX, TY = sh == 1 ? tile_shape<1>::TY : tile_shape<0>::TY;
   f->d = d;
   f->gx2 = f->gy2 = f->x2_off = 0;
@@ -1178,9 +1078,9 @@ void fused_grid(fused_args* f, const pp_dims& d, int occupancy, int sh, char ker
     f->gx2 = 1;
     f->gy2 = (d.ny + tile_shape<1>::TY - 1) / tile_shape<1>::TY;
     f->x2_off = f->gx * tile_shape<0>::TX;
-    f->zchunk = fused_zchunk(d, 256 * occupancy, TX, TY, nullptr, kernel, f->gx * f->gy + f->gx2 * f->gy2);
+    f->zchunk = fused_zchunk(d, 256 * occupancy, TX, TY, nullptr, f->gx * f->gy + f->gx2 * f->gy2);
   } else {
-    f->zchunk = fused_zchunk(d, 256 * occupancy, TX, TY, nullptr, kernel);
+    f->zchunk = fused_zchunk(d, 256 * occupancy, TX, TY);
     f->gx = (d.nx + TX - 1) / TX;
     f->gy = (d.ny + TY - 1) / TY;
   }
@@ -1200,11 +1100,8 @@ void fused_grid(fused_args* f, const pp_dims& d, int occupancy, int sh, char ker
               (size_t)d.nx * d.ny * d.nz >= ((size_t)8 << 20);
   if (const char* e = pp_env("PP_FUSED_MASK"))   // (0: the branchy kernels; 1: MASK wherever the shape allows -- A/B runs, tests)
     f->masked = atoi(e) != 0 && (f->px % 2 == 0) && 3 * (size_t)f->px * d.ny * d.nz * sizeof(float) < ((size_t)1 << 31);
-  // soft synchronisation (PP_SOFTSYNC builds, MASK instances): only when every block of an XCD's run is resident at once --
-  // 32 CUs x `occupancy` slots -- since a block waits for the MEAN progress of its group (pp_demons_fused2.h)
   f->sync = f->sync_other = nullptr;   // (set by the caller once the workspace is carved)
-  f->sync_lag = (PP_SOFTSYNC > 0 && f->per_xcd <= 32 * occupancy) ? PP_SOFTSYNC : 0;
-  if (const char* e = pp_env("PP_FUSED_SYNC")) f->sync_lag = (f->per_xcd <= 32 * occupancy) ? atoi(e) : 0;
+  f->unused_slot = 0;
 }
 
 int check_demons_args(pp_ctx* ctx, const pp_geom* g, const pp_demons_params* p) {
@@ -1361,16 +1258,13 @@ int pp_demons_execute_f32(pp_ctx* ctx, const float* fixed, const float* moving, 
     if (tu[a].r > ra) ra = tu[a].r;
     if (td[a].r > rb) rb = td[a].r;
   }
-  int opt = PP_FUSED_DEFAULT_OPT;
-  if (const char* e = pp_env("PP_FUSED_OPT")) opt = atoi(e) == 2 ? 2 : 4;
   // kernel generation: 2 (pp_demons_fused2.h) unless the volume exceeds its 32-bit gather offsets / 24-bit row arithmetic,
-  // rows are shorter than one strip, the 256-thread layout was asked for, or PP_FUSED_GEN=1 selects the first generation
-  // (kept for A/B measurements).
+  // rows are shorter than one strip, or PP_FUSED_GEN=1 selects the first generation (kept for A/B measurements).
   // (a scalar image under one buffer resource's 32-bit offsets; a 3-component field beyond that takes the BIG instances)
   const bool gen2_ok = N * sizeof(float) < ((size_t)1 << 32) &&
                        (size_t)d.ny * d.nz < ((size_t)1 << 24) && d.nx >= 4 && d.nx < (1 << 22) &&
                        d.ny < (1 << 22) && d.nz < (1 << 22);   // (every axis below the warp's 2^23-voxel displacement clamp)
-  int gen = (gen2_ok && opt == 2) ? 2 : 1;
+  int gen = gen2_ok ? 2 : 1;
   if (const char* e = pp_env("PP_FUSED_GEN")) {
     if (atoi(e) == 1) gen = 1;
   }
@@ -1385,7 +1279,6 @@ int pp_demons_execute_f32(pp_ctx* ctx, const float* fixed, const float* moving, 
   }
   // fields of >= 2^32 bytes: generation 2 serves them through its BIG instances, which exist for the SUM pair only
   if (3 * N * sizeof(float) >= ((size_t)1 << 32) && !sum_mode) gen_a = gen_b = 1;
-  const int opt_a = ra > 3 ? 2 : opt, opt_b = rb > 3 ? 2 : opt;   // radii 4 and 5 exist in the 512-thread layout only
   fused_args fu, fd;
   int sh_a = 0, sh_b = 0;
   // Padded rows (fused_args::px) when both kernels are generation 2 in SUM mode and the rows are not whole 16-byte quads.
@@ -1409,14 +1302,13 @@ int pp_demons_execute_f32(pp_ctx* ctx, const float* fixed, const float* moving, 
     cube = cube && atoi(e) != 0;
   } else {
     // (a switch addressed to the marching kernels selects them: A/B runs and the tests of their variants keep their meaning)
-    for (const char* name : {"PP_FUSED_GEN", "PP_FUSED_TILE", "PP_FUSED_MASK", "PP_FUSED_MIX", "PP_FUSED_NT", "PP_FUSED_OPT", "PP_FUSED_PITCH",
-                             "PP_FUSED_SYNC", "PP_FUSED_ZCHUNK", "PP_FUSED_ZCHUNK_A", "PP_FUSED_ZCHUNK_B"})
+    for (const char* name : {"PP_FUSED_GEN", "PP_FUSED_TILE", "PP_FUSED_MASK", "PP_FUSED_MIX", "PP_FUSED_NT", "PP_FUSED_PITCH", "PP_FUSED_ZCHUNK"})
       if (pp_env(name)) cube = false;
     cube = cube && cube_bricks(d) <= CUBE_MAX_BRICKS;
   }
   cube_args cu, cd;
   cu.d = cd.d = d;
-  // tile shape per kernel: 32 x 32 where the z-chunk model says the 64 x 16 launch wastes >= 10 % (512-thread layouts only)
+  // tile shape per kernel: 32 x 32 where the z-chunk model says the 64 x 16 launch wastes >= 10 %
   if (gen_a == 2) {
 #define PP_OCC_A20(RR) occ_force2<RR>(0)
 #define PP_OCC_A21(RR) occ_force2<RR>(1)
@@ -1427,20 +1319,19 @@ int pp_demons_execute_f32(pp_ctx* ctx, const float* fixed, const float* moving, 
 #define PP_OCC_A22(RR) occ_force2<RR>(2)
     if (fused_mix_ok(d) && !pp_env("PP_FUSED_TILE")) {
       sh_a = 2;
-      fused_grid(&fu, d, PP_BY_RADIUS_A2(ra, PP_OCC_A22), 2, 'A', px);
+      fused_grid(&fu, d, PP_BY_RADIUS_A2(ra, PP_OCC_A22), 2, px);
     } else {
-      fused_grid(&fu, d, sh_a ? occ_a1 : occ_a0, sh_a, 'A', px);
+      fused_grid(&fu, d, sh_a ? occ_a1 : occ_a0, sh_a, px);
     }
 #undef PP_OCC_A22
   } else {
-#define PP_OCC_A0(RR, OO) occ_force_sh<RR, OO>(0)
-#define PP_OCC_A1(RR, OO) occ_force_sh<RR, OO>(1)
-    const int occ_a0 = PP_BY_RADIUS(ra, opt_a, PP_OCC_A0);
-    const int occ_a1 = opt_a == 2 ? PP_BY_RADIUS(ra, opt_a, PP_OCC_A1) : occ_a0;
+#define PP_OCC_A0(RR) occ_force_sh<RR>(0)
+#define PP_OCC_A1(RR) occ_force_sh<RR>(1)
+    const int occ_a0 = PP_BY_RADIUS(ra, PP_OCC_A0), occ_a1 = PP_BY_RADIUS(ra, PP_OCC_A1);
 #undef PP_OCC_A0
 #undef PP_OCC_A1
-    sh_a = opt_a == 2 ? fused_shape(d, 256 * occ_a0, 256 * occ_a1) : 0;
-    fused_grid(&fu, d, sh_a ? occ_a1 : occ_a0, sh_a, 'A');
+    sh_a = fused_shape(d, 256 * occ_a0, 256 * occ_a1);
+    fused_grid(&fu, d, sh_a ? occ_a1 : occ_a0, sh_a);
   }
   if (gen_b == 2) {
 #define PP_OCC_B20(RR) occ_warp2<RR>(0)
@@ -1452,20 +1343,19 @@ int pp_demons_execute_f32(pp_ctx* ctx, const float* fixed, const float* moving, 
 #define PP_OCC_B22(RR) occ_warp2<RR>(2)
     if (fused_mix_ok(d) && !pp_env("PP_FUSED_TILE")) {
       sh_b = 2;
-      fused_grid(&fd, d, PP_BY_RADIUS_B2(rb, PP_OCC_B22), 2, 'B', px);
+      fused_grid(&fd, d, PP_BY_RADIUS_B2(rb, PP_OCC_B22), 2, px);
     } else {
-      fused_grid(&fd, d, sh_b ? occ_b1 : occ_b0, sh_b, 'B', px);
+      fused_grid(&fd, d, sh_b ? occ_b1 : occ_b0, sh_b, px);
     }
 #undef PP_OCC_B22
   } else {
-#define PP_OCC_B0(RR, OO) occ_warp_sh<RR, OO>(0)
-#define PP_OCC_B1(RR, OO) occ_warp_sh<RR, OO>(1)
-    const int occ_b0 = PP_BY_RADIUS(rb, opt_b, PP_OCC_B0);
-    const int occ_b1 = opt_b == 2 ? PP_BY_RADIUS(rb, opt_b, PP_OCC_B1) : occ_b0;
+#define PP_OCC_B0(RR) occ_warp_sh<RR>(0)
+#define PP_OCC_B1(RR) occ_warp_sh<RR>(1)
+    const int occ_b0 = PP_BY_RADIUS(rb, PP_OCC_B0), occ_b1 = PP_BY_RADIUS(rb, PP_OCC_B1);
 #undef PP_OCC_B0
 #undef PP_OCC_B1
-    sh_b = opt_b == 2 ? fused_shape(d, 256 * occ_b0, 256 * occ_b1) : 0;
-    fused_grid(&fd, d, sh_b ? occ_b1 : occ_b0, sh_b, 'B');
+    sh_b = fused_shape(d, 256 * occ_b0, 256 * occ_b1);
+    fused_grid(&fd, d, sh_b ? occ_b1 : occ_b0, sh_b);
   }
   small_taps(tu[0], ra, &fu.wx);
   small_taps(tu[1], ra, &fu.wy);
@@ -1502,14 +1392,14 @@ int pp_demons_execute_f32(pp_ctx* ctx, const float* fixed, const float* moving, 
   double* partials2 = cv.take<double>(3 * nblk);   // generation-2 kernel A alternates: it folds the previous launch's sums itself
   pp_dev_stats* dst = cv.take<pp_dev_stats>(1);
   const int* halt = &dst->halt;
-  {   // progress counters of the soft synchronisation: kernel A's set, kernel B's set (each launch clears the other's)
+  {   // progress words of the pair priority: kernel A's set, kernel B's set (each launch clears the other's)
     unsigned* const sync_words = cv.take<unsigned>(2 * SYNC_WORDS);
     fu.sync = sync_words;
     fu.sync_other = sync_words + SYNC_WORDS;
     fd.sync = sync_words + SYNC_WORDS;
     fd.sync_other = sync_words;
     // (only the MASK instances publish progress: the latency-bound levels do not pay for the memset)
-    if ((PP_SOFTSYNC > 0 || PP_PAIRPRIO > 0) && (fu.masked || fd.masked))
+    if (fu.masked || fd.masked)
       PP_HIP(ctx, hipMemsetAsync(sync_words, 0, 2 * SYNC_WORDS * sizeof(unsigned), ctx->stream));
   }
   hipLaunchKernelGGL(k_stats_init, dim3(1), dim3(1), 0, ctx->stream, dst, hist, ctx->hist_cap);
@@ -1543,8 +1433,8 @@ int pp_demons_execute_f32(pp_ctx* ctx, const float* fixed, const float* moving, 
       rc = PP_BY_RADIUS_A2(ra, PP_CALL_A2);
 #undef PP_CALL_A2
     } else {
-#define PP_CALL_A(RR, OO) launch_force<RR, OO>(ctx, sh_a, fixed, mw_in, Us, fu, K, partials, halt)
-      rc = PP_BY_RADIUS(ra, opt_a, PP_CALL_A);
+#define PP_CALL_A(RR) launch_force<RR>(ctx, sh_a, fixed, mw_in, Us, fu, K, partials, halt)
+      rc = PP_BY_RADIUS(ra, PP_CALL_A);
 #undef PP_CALL_A
     }
     PP_LAUNCH_CHECK(ctx, "k_fused_force_smooth");
@@ -1558,8 +1448,8 @@ int pp_demons_execute_f32(pp_ctx* ctx, const float* fixed, const float* moving, 
       rc = PP_BY_RADIUS_B2(rb, PP_CALL_B2);
 #undef PP_CALL_B2
     } else {
-#define PP_CALL_B(RR, OO) launch_warp<RR, OO>(ctx, sh_b, Dcur, (const float*)Us, moving, Dnext, mw_out, fd, sc, halt)
-      rc = PP_BY_RADIUS(rb, opt_b, PP_CALL_B);
+#define PP_CALL_B(RR) launch_warp<RR>(ctx, sh_b, Dcur, (const float*)Us, moving, Dnext, mw_out, fd, sc, halt)
+      rc = PP_BY_RADIUS(rb, PP_CALL_B);
 #undef PP_CALL_B
     }
     PP_LAUNCH_CHECK(ctx, "k_fused_add_smooth_warp");
@@ -1609,29 +1499,5 @@ int pp_demons_history(pp_ctx* ctx, double* metric, double* rms_change, int cap) 
   }
   return ran > n ? ran : n;
 }
-
-#ifdef PP_DRIFT
-int pp_debug_drift_read(unsigned long long* out, int cap) {
-  const int n = 2 * 1024 * 4;
-  if (cap < n) return -1;
-  if (hipMemcpyFromSymbol(out, HIP_SYMBOL(pp_drift_buf), sizeof(unsigned long long) * n) != hipSuccess) return -2;
-  return n;
-}
-int pp_debug_drift_xcc_read(unsigned* out, int cap) {
-  const int n = 2 * 1024;
-  if (cap < n) return -1;
-  if (hipMemcpyFromSymbol(out, HIP_SYMBOL(pp_drift_xcc), sizeof(unsigned) * n) != hipSuccess) return -2;
-  return n;
-}
-#endif
-
-#ifdef PP_TRACE
-int pp_debug_trace_read(unsigned* out, int cap) {
-  const int n = 2 * 8 * PP_TRACE_STEPS * PP_TRACE_SLOTS;
-  if (cap < n) return -1;
-  if (hipMemcpyFromSymbol(out, HIP_SYMBOL(pp_trace_buf), sizeof(unsigned) * n) != hipSuccess) return -2;
-  return n;
-}
-#endif
 
 }  // extern "C"

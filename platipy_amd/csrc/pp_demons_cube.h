@@ -57,7 +57,7 @@ __device__ __forceinline__ void cube_xpass(const float* __restrict__ s_u, float*
       const float4 v = *reinterpret_cast<const float4*>(src + 4 * k);
       in[4 * k + 0] = v.x; in[4 * k + 1] = v.y; in[4 * k + 2] = v.z; in[4 * k + 3] = v.w;
     }
-    if ((4 + 2 * R) % 4 == 2) {
+    if constexpr ((4 + 2 * R) % 4 == 2) {
       const float2 v = *reinterpret_cast<const float2*>(src + (4 + 2 * R) / 4 * 4);
       in[(4 + 2 * R) / 4 * 4 + 0] = v.x;
       in[(4 + 2 * R) / 4 * 4 + 1] = v.y;

@@ -22,18 +22,7 @@
 
 // Register budget: 4 waves per SIMD = two 512-thread blocks per CU (<= 128 VGPRs); without the bound the scheduler
 // spends up to ~170 registers on load latency it cannot use with one block per CU.
-#ifndef PP_A_XASM
-#define PP_A_XASM 1
-#endif
-#ifndef PP_B_XSHFL
-#define PP_B_XSHFL 1
-#endif
-#ifndef PP_B_DEFER
-#define PP_B_DEFER 1
-#endif
-#ifndef PP_GEN2_WAVES
-#define PP_GEN2_WAVES 4
-#endif
+constexpr int GEN2_WAVES = 4;
 
 #include "pp_warp_sample.h"
 
@@ -64,28 +53,14 @@ __device__ __forceinline__ void pp_gst2(char* base, unsigned byte_off, float a, 
   *reinterpret_cast<pp_f2u*>(base + (size_t)byte_off) = v;
 }
 // The same load with a wave-uniform byte offset in the instruction's scalar-offset operand: one resource per ARRAY is
-// built once per block and a plane / component is a 32-bit scalar (PP_SOFF=1, the default; callers guarantee that the whole
-// array spans < 2^32 bytes).  Rebuilding a 64-bit base + resource per plane and array cost kernel A ~45 scalar instructions
-// per plane and both kernels the scalar registers whose spills (v_readlane) sat in the plane loop.
-#ifndef PP_SOFF
-#define PP_SOFF 1
-#endif
+// built once per block and a plane / component is a 32-bit scalar (callers guarantee that the whole array spans < 2^32
+// bytes).  Rebuilding a 64-bit base + resource per plane and array cost kernel A ~45 scalar instructions per plane and both
+// kernels the scalar registers whose spills (v_readlane) sat in the plane loop.
 __device__ __forceinline__ float pp_blds(pp_rsrc r, unsigned byte_off, unsigned s_off) {
   return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r, byte_off, s_off, 0));
 }
-// Cache-policy bits of the buffer stores (2 = nt, streaming) for builds that force one policy; the product chooses per
-// launch, see pp_bst2 below.
-#ifndef PP_STORE_AUX
-#define PP_STORE_AUX 0
-#endif
 __device__ __forceinline__ void pp_bst(pp_rsrc r, unsigned byte_off, float a) {
-  __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, a), r, byte_off, 0, PP_STORE_AUX);
-}
-__device__ __forceinline__ void pp_bst2(pp_rsrc r, unsigned byte_off, float a, float b) {
-  pp_u2 v;
-  v[0] = __builtin_bit_cast(unsigned, a);
-  v[1] = __builtin_bit_cast(unsigned, b);
-  __builtin_amdgcn_raw_buffer_store_b64(v, r, byte_off, 0, PP_STORE_AUX);
+  __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, a), r, byte_off, 0, 0);
 }
 // Pair store with the cache policy picked per launch (a kernel template parameter): streaming (nt) when the iteration's working set
 // is far larger than the 256 MB infinity cache -- the outputs are read next by the OTHER kernel, long after they have left
@@ -107,7 +82,7 @@ __device__ __forceinline__ void pp_bst2ss(pp_rsrc r, unsigned byte_off, unsigned
   __builtin_amdgcn_raw_buffer_store_b64(v, r, byte_off, s_off, STREAMING ? 2 : 0);
 }
 __device__ __forceinline__ void pp_bsts(pp_rsrc r, unsigned byte_off, unsigned s_off, float a) {
-  __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, a), r, byte_off, s_off, PP_STORE_AUX);
+  __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, a), r, byte_off, s_off, 0);
 }
 
 // Sum of three doubles over the block: butterfly inside each wavefront (ds_bpermute shuffles, no LDS
@@ -217,7 +192,7 @@ __device__ __forceinline__ void pp_strip_remap_lds(float* strip, int cstride, un
 // and a 16-byte lane stride: 2- and 4-way bank conflicts, most of kernel A's 34 % LDS conflict cycles.)  The wait is in the
 // statement because the compiler does not count loads it cannot see.
 __device__ __forceinline__ void pp_lds_read2x128(const float* p, float4& a, float4& b) {
-#if defined(__HIP_DEVICE_COMPILE__) && PP_A_XASM
+#if defined(__HIP_DEVICE_COMPILE__)
   const unsigned addr = (unsigned)(size_t)p;   // (LDS pointers are 32-bit offsets in the low half of a flat address)
   asm volatile("ds_read_b128 %0, %2\n\tds_read_b128 %1, %2 offset:16\n\ts_waitcnt lgkmcnt(0)" : "=&v"(a), "=&v"(b) : "v"(addr) : "memory");
 #else
@@ -264,18 +239,15 @@ __device__ __forceinline__ void fused2_xpass(const float* __restrict__ us, float
   }
 }
 
-// Kernel A's x-pass tile s_x: row pitch.  With PP_A_XPERM the lanes of a wave are dealt to (row, column group) items so that
+// Kernel A's x-pass tile s_x: row pitch.  With 64-wide tiles the lanes of a wave are dealt to (row, column group) items so that
 // every lane group the hardware services a ds_read_b128 in -- {0-3,12-15,20-27}, {4-11,16-19,28-31} and the same + 32
 // (MI355X_MICROARCH.md, LDS) -- reads ONE row's 16 consecutive 16-byte groups: 64 consecutive banks, no conflict, whatever
 // the pitch of the source tile (in plain lane order a group straddles two rows 68 floats apart and one bank quartet is hit
 // twice: every x-pass read ran at half rate, half of kernel A's 34 % LDS conflict cycles).  The 8-lane groups of the
 // ds_write_b128 then hold quarter rows of TWO rows; the pitch of s_x moves them 16 banks apart (64 + 16 floats).
-#ifndef PP_A_XPERM
-#define PP_A_XPERM 1
-#endif
 template <int SH>
 struct fused2_xtile {
-  static constexpr bool PERM = (PP_A_XPERM != 0) && tile_shape<SH>::TX == 64;
+  static constexpr bool PERM = tile_shape<SH>::TX == 64;
   static constexpr int XP = tile_shape<SH>::TX + (PERM ? 16 : 0);   // row pitch of s_x (floats)
 };
 __device__ __forceinline__ int fused2_xperm_lane(int lane) {   // lane of a wave -> position in the wave's item order
@@ -291,7 +263,7 @@ __device__ __forceinline__ int fused2_xperm_lane(int lane) {   // lane of a wave
 }
 template <int R, int SH, int NXI>
 __device__ __forceinline__ void fused2_xpass_setup(int t, int (&xsrc)[NXI], int (&xdst)[NXI]) {
-  using G = fused_geom<R, 2, SH>;
+  using G = fused_geom<R, SH>;
   constexpr int XP = fused2_xtile<SH>::XP;
   const int tp = fused2_xtile<SH>::PERM ? ((t & ~63) | fused2_xperm_lane(t & 63)) : t;
 #pragma unroll
@@ -314,7 +286,7 @@ __device__ __forceinline__ void fused2_xpass_setup(int t, int (&xsrc)[NXI], int 
 // y pass: this thread's two outputs of component c (s_x row pitch XP, `yb` = cy * XP + 2 cx).
 template <int R, int SH>
 __device__ __forceinline__ void fused2_ypass(const float* __restrict__ xs, int c, int yb, const pp_taps_small& wy, float v[2]) {
-  using G = fused_geom<R, 2, SH>;
+  using G = fused_geom<R, SH>;
   constexpr int XP = fused2_xtile<SH>::XP;
   v[0] = 0.0f;
   v[1] = 0.0f;
@@ -499,177 +471,20 @@ __device__ __forceinline__ void fused2_plane_loop(F& step, int nsteps) {
     for (int n = 0; n < nsteps; ++n) step(n, pp_phase<-1>{});
   }
 }
-// Round 4: the plane loop in three parts.  Steps s_lo <= n < s_hi are STEADY: every wave-uniform condition of the step (a
-// fresh plane either side, an output plane, a plane to prefetch, every lane inside the volume) holds, so `step(n, phase,
-// pp_steady<true>)` is straight-line code around its memory instructions.  That matters for more than the branches: the
-// hardware's vmcnt counts loads AND stores in issue order and the compiler's s_waitcnt pass merges the states of all paths
-// into a step, so with the conditions dynamic every wait for an old load was emitted as the wait of the worst path --
-// vmcnt(0) right behind the warp's gathers, between the field stores, at the top of a step -- and each wave sat out the
-// acknowledgement of the stores and the HBM latency of the loads it had issued a moment earlier (47-61 % of wave cycles in
-// SQ_WAIT_ANY, profiles/round3_pmc_counters.md).  The steady steps run in whole groups of 2R+1 window phases (renamed z
-// window); the steps before and after run the general step with the shifting window (P = -1), whose window order equals the
-// renamed one's at every group boundary.
-template <bool B>
-struct pp_steady { static constexpr bool value = B; };
-template <int P, int W>
-struct pp_steady_unroll {
-  template <class F>
-  static __device__ __forceinline__ void run(F& step, int n0) {
-    step(n0 + P, pp_phase<P>{}, pp_steady<true>{});
-    pp_steady_unroll<P + 1, W>::run(step, n0);
-  }
-};
-template <int W>
-struct pp_steady_unroll<W, W> {
-  template <class F>
-  static __device__ __forceinline__ void run(F&, int) {}
-};
-#ifndef PP_STEADY
-#define PP_STEADY 0
-#endif
-#ifndef PP_A_SPLIT_LDS
-#define PP_A_SPLIT_LDS 1
-#endif
-#ifndef PP_B_XLATE
-#define PP_B_XLATE 1
-#endif
-#ifndef PP_B_VOTE
-#define PP_B_VOTE 1
-#endif
-#ifndef PP_A_VOTE
-#define PP_A_VOTE 1
-#endif
-#ifndef PP_A_ESM_PAIRS
-#define PP_A_ESM_PAIRS 1
-#endif
-#ifndef PP_A_FLIP
-#define PP_A_FLIP 0   // (measured, tools/r5/gpu6.sh: kernel B's role flip -1 % on B in three alternating rounds, kernel A's none)
-#endif
-#ifndef PP_B_FLIP
-#define PP_B_FLIP 1
-#endif
-#ifndef PP_B_FINISH_AFTER_BARRIER
-#define PP_B_FINISH_AFTER_BARRIER 1
-#endif
-#ifndef PP_A_STEADY
-#define PP_A_STEADY 0
-#endif
-template <int R, bool UNROLL, class F>
-__device__ __forceinline__ void fused2_plane_loop3(F& step, int nsteps, int s_lo, int s_hi) {
-  constexpr int W = 2 * R + 1;
-  int n = 0;
-  if (s_hi - s_lo >= (UNROLL ? W : 1)) {
-    for (; n < s_lo; ++n) step(n, pp_phase<-1>{}, pp_steady<false>{});
-    if constexpr (UNROLL) {
-      for (; n + W <= s_hi; n += W) pp_steady_unroll<0, W>::run(step, n);
-    } else {
-      for (; n < s_hi; ++n) step(n, pp_phase<-1>{}, pp_steady<true>{});
-    }
-  }
-  for (; n < nsteps; ++n) step(n, pp_phase<-1>{}, pp_steady<false>{});
-}
 
-
-// ---- Round 5: soft synchronisation of the blocks that share an L2 -------------------------------------------------------
-// The x/y halo of a tile (two 16-byte strips a row in x, 2R rows in y) lies in cache lines that belong to the NEIGHBOUR tiles:
-// a block finds them in its XCD's L2 only while the neighbour's march is within a plane or two of its own (4 MB of L2 see
-// ~1-2 MB of traffic per plane step of the 64 resident blocks).  Nothing keeps them there: measured with -DPP_DRIFT, the 64
-// blocks of an XCD are spread over 45 (kernel A) to 70 (kernel B) plane steps of a 132-step march (the two blocks of a CU do
-// not share it evenly), and kernel B's fetch swings between 1.13 and 1.6 x its compulsory reads with launch timing.
-// With PP_SOFTSYNC each block of an XCD (block b runs on XCD b % 8, the assumption the tile order already makes -- speed
-// only) publishes the number of plane steps it has finished in a word of its own, and starts step n + 1 only when EVERY
-// block of its group has finished step n + 1 - lag: the leaders wait, nobody else.
-//   * Plain stores and L1-bypassing loads (workgroup scope: `global_store / global_load sc0`), both served by the XCD's own
-//     L2.  Not atomics: on this part a device atomic is executed beyond the L2 and takes microseconds, and since a wave's
-//     memory instructions retire in issue order every younger load of the step waited behind it -- the first two versions
-//     (one counter per XCD, agent- and workgroup-scope fetch_add) ran the kernels 2.7-4 x slower (profiles/round5_softsync.md).
-//   * The wait is bounded: a group that is not co-resident, or a dispatcher that spreads a group over XCDs (whose L2s would
-//     then each see their own blocks' words only), costs one time-out per block and switches that block's waiting off.
-//     Slower, never wrong, and no launch can hang on it.
-//   * One wave per block does all of it; the words it tests were requested a whole step earlier.
-#ifndef PP_SOFTSYNC
-#define PP_SOFTSYNC 0
-#endif
-#ifndef PP_SOFTSYNC_TRIES
-#define PP_SOFTSYNC_TRIES 24
-#endif
-constexpr unsigned PP_SYNC_GROUP = 64;      // words per XCD: one per resident block (2 blocks x 32 CUs)
-constexpr unsigned PP_SYNC_DONE = 0x40000000u;
-struct pp_softsync {
-  unsigned* words;   // this XCD's PP_SYNC_GROUP progress words
-  unsigned* mine;    // this block's word
-  const unsigned* peek_at;   // the word this LANE watches (wave 0: lane l watches block l of the group)
-  unsigned seen;     // ... as last read
-  int lag;           // <= 0: publish only
-  bool wave0;        // this wave publishes and waits for its block (wave-uniform, held in scalar registers)
-};
-#ifndef PP_SOFTSYNC_LOAD_SCOPE
-#define PP_SOFTSYNC_LOAD_SCOPE __HIP_MEMORY_SCOPE_WORKGROUP
-#endif
-#ifndef PP_SOFTSYNC_STORE_SCOPE
-#define PP_SOFTSYNC_STORE_SCOPE __HIP_MEMORY_SCOPE_WORKGROUP
-#endif
-__device__ __forceinline__ unsigned pp_sync_peek(const unsigned* w) { return __hip_atomic_load(w, __ATOMIC_RELAXED, PP_SOFTSYNC_LOAD_SCOPE); }
-__device__ __forceinline__ void pp_softsync_init(pp_softsync& y, const fused_args& a, unsigned* other_set) {
-  const unsigned xcd = blockIdx.x & 7u, j = blockIdx.x >> 3;
-  const unsigned ntiles = ((unsigned)a.gx * a.gy + (unsigned)a.gx2 * a.gy2) * (unsigned)a.gz;
-  const unsigned first = xcd * (unsigned)a.per_xcd;
-  const unsigned group = ntiles > first ? (ntiles - first < (unsigned)a.per_xcd ? ntiles - first : (unsigned)a.per_xcd) : 0u;
-  y.words = a.sync + xcd * PP_SYNC_GROUP;
-  y.mine = y.words + (j < PP_SYNC_GROUP ? j : 0u);
-  const unsigned lane = threadIdx.x & 63u;
-  y.peek_at = (lane < group && lane < PP_SYNC_GROUP) ? y.words + lane : y.mine;
-  y.seen = 0u;
-  y.lag = (group <= PP_SYNC_GROUP && j < PP_SYNC_GROUP) ? a.sync_lag : 0;
-  y.wave0 = __builtin_amdgcn_readfirstlane((int)threadIdx.x) < 64;
-  // the OTHER kernel's words are idle while this launch runs: clear this block's for that kernel's next launch
-  if (threadIdx.x == 0 && j < PP_SYNC_GROUP) __hip_atomic_store(other_set + xcd * PP_SYNC_GROUP + j, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-}
-// Start of a plane step: request the group's words (consumed at the end of the step).
-__device__ __forceinline__ void pp_softsync_peek(pp_softsync& y) {
-  if (y.wave0) y.seen = pp_sync_peek(y.peek_at);
-}
-// End of plane step n (0-based) of a block, ahead of the barrier that closes the step; every wave calls it, wave 0 acts.
-__device__ __forceinline__ void pp_softsync_step(pp_softsync& y, int n) {
-  if (y.wave0) {
-    if (threadIdx.x == 0) __hip_atomic_store(y.mine, (unsigned)(n + 1), __ATOMIC_RELAXED, PP_SOFTSYNC_STORE_SCOPE);
-    if (y.lag > 0 && n + 1 > y.lag) {
-      const unsigned need = (unsigned)(n + 1 - y.lag);
-      if (__any(y.seen < need)) {
-        int tries = 0;
-        bool behind;
-        do {
-          __builtin_amdgcn_s_sleep(4);
-          behind = __any(pp_sync_peek(y.peek_at) < need);
-        } while (behind && ++tries < PP_SOFTSYNC_TRIES);
-        if (behind) y.lag = 0;   // timed out: this block stops waiting (it still publishes)
-      }
-    }
-  }
-}
-// ---- Round 5: the two blocks of a CU, kept level by wave priority ------------------------------------------------------
-// -DPP_DRIFT shows where the drift comes from: block b + 256 of a 512-block launch -- the SECOND block on the CU that block b
-// got first (XCD-local indices j and j + 32) -- finishes 75-115 us (kernel A) / 125-175 us (kernel B) after block b, every pair,
+// ---- The two blocks of a CU, kept level by wave priority ----------------------------------------------------------------
+// Clock stamps of every block at the quarter points of its march show where the drift comes from: block b + 256 of a
+// 512-block launch -- the SECOND block on the CU that block b got first (XCD-local indices j and j + 32) -- finishes 75-115 us (kernel A) / 125-175 us (kernel B) after block b, every pair,
 // while the first blocks of an XCD finish within 20 us of each other: the SIMD arbiter serves the older wave first, so the older
 // block runs as if alone and the younger one fills its gaps, and for the last fifth to third of the launch every CU runs ONE
-// block (8 waves: half the latency hiding).  With PP_PAIRPRIO each block publishes its finished plane steps (the soft barrier's
-// words), reads its partner's once a step, and every wave of the block that is BEHIND raises its issue priority (s_setprio) for
+// block (8 waves: half the latency hiding).  So each block publishes its finished plane steps in a progress word of its own,
+// reads its partner's once a step, and every wave of the block that is BEHIND raises its issue priority (s_setprio) for
 // the next step: bang-bang control that keeps the pair within a step or two of each other, so that both finish together and
 // the CU runs two blocks to the end.  Wrong pairing (another dispatcher, another kernel's block as neighbour) only means a
-// priority that helps nobody.
-#ifndef PP_PAIRPRIO
-#define PP_PAIRPRIO 1   // (measured, tools/kbench/ab.sh main prio1 ...: pair end difference 97 / 153 us -> 6 us, iteration -1.9 .. -3.5 % at
-                        // 512 x 512 x 256, -3 % at 341 x 341 x 171, kernel B's fetch -11 %; profiles/round5_pair_priority.md)
-#endif
-#ifndef PP_PAIRPRIO_LEVEL
-#define PP_PAIRPRIO_LEVEL 1
-#endif
-#ifndef PP_PAIRPRIO_ASYM
-#define PP_PAIRPRIO_ASYM 0    // (measurement: the second block of a pair tolerates being this many more steps behind -- an anti-phase pair)
-#endif
-#ifndef PP_PAIRPRIO_SLACK
-#define PP_PAIRPRIO_SLACK 1   // behind = the partner's count (a step old) exceeds this block's finished steps n + 1 - 1 + SLACK
-#endif
+// priority that helps nobody.  (Measured: pair end difference 97 / 153 us -> 6 us, iteration -1.9 .. -3.5 % at 512 x 512 x 256,
+// -3 % at 341 x 341 x 171, kernel B's fetch -11 %; profiles/round5_pair_priority.md.)
+constexpr unsigned PP_SYNC_GROUP = 64;      // words per XCD: one per resident block (2 blocks x 32 CUs)
+constexpr unsigned PP_SYNC_DONE = 0x40000000u;
 struct pp_pairprio {
   unsigned* mine;            // this block's progress word
   const unsigned* partner;   // the progress word of the block that shares the CU
@@ -697,34 +512,15 @@ __device__ __forceinline__ void pp_pairprio_peek(pp_pairprio& y) {   // every wa
 __device__ __forceinline__ void pp_pairprio_step(pp_pairprio& y, int n) {
   if (y.wave0 && threadIdx.x == 0) __hip_atomic_store(y.mine, (unsigned)(n + 1), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
   if (y.has) {
+    // behind: the partner's count (a step old) exceeds n + 1, the steps this block has finished
     const unsigned theirs = (unsigned)__builtin_amdgcn_readfirstlane((int)y.seen);
-    if (theirs > (unsigned)(n + PP_PAIRPRIO_SLACK + (PP_PAIRPRIO_ASYM ? (int)((blockIdx.x >> 8) & 1u) * PP_PAIRPRIO_ASYM : 0))) __builtin_amdgcn_s_setprio(PP_PAIRPRIO_LEVEL);
+    if (theirs > (unsigned)(n + 1)) __builtin_amdgcn_s_setprio(1);
     else __builtin_amdgcn_s_setprio(0);
   }
 }
 __device__ __forceinline__ void pp_pairprio_finish(pp_pairprio& y) {
   if (threadIdx.x == 0) __hip_atomic_store(y.mine, PP_SYNC_DONE, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
 }
-
-// A block that has finished its march never holds anybody back.
-__device__ __forceinline__ void pp_softsync_finish(pp_softsync& y) {
-  if (threadIdx.x == 0) __hip_atomic_store(y.mine, PP_SYNC_DONE, __ATOMIC_RELAXED, PP_SOFTSYNC_STORE_SCOPE);
-}
-// Measurement builds (-DPP_DRIFT, tools/kbench): 100 MHz wall-clock stamps of EVERY block at the quarter points of its march.
-#ifdef PP_DRIFT
-__device__ unsigned long long pp_drift_buf[2][1024][4];
-__device__ unsigned pp_drift_xcc[2][1024];   // HW_REG_XCC_ID of the block's first wave: which XCD did block b really run on?
-#define PP_DRIFT_MARK(kern, n, nsteps)                                                                                  \
-  do {                                                                                                                  \
-    if (threadIdx.x == 0 && blockIdx.x < 1024) {                                                                        \
-      const int q_ = ((n) == (nsteps) / 4) ? 0 : ((n) == (nsteps) / 2) ? 1 : ((n) == 3 * (nsteps) / 4) ? 2 : ((n) == (nsteps)-1) ? 3 : -1; \
-      if (q_ >= 0) pp_drift_buf[kern][blockIdx.x][q_] = wall_clock64();                                                 \
-      if (q_ == 0) pp_drift_xcc[kern][blockIdx.x] = __builtin_amdgcn_s_getreg(20 | (0 << 6) | (31 << 11));              \
-    }                                                                                                                   \
-  } while (0)
-#else
-#define PP_DRIFT_MARK(kern, n, nsteps) do { } while (0)
-#endif
 
 // ---- kernel B, generation 2: D' = G_d * (D + U), then the next iteration's warped moving image --------
 // SUM: `Us` already holds D + U (kernel A<SUM> added D at its own output voxels, where it needs no halo), `D` is not read:
@@ -740,14 +536,14 @@ __device__ unsigned pp_drift_xcc[2][1024];   // HW_REG_XCC_ID of the block's fir
 template <int R, int SH, bool SUM>
 struct fused2_warp_lds {
   using G = strip_geom<R, SH, 0>;
-  static constexpr bool XS = (PP_B_XSHFL != 0) && SUM;
+  static constexpr bool XS = SUM;
   static constexpr int N = XS ? 2 * G::SZ_X : G::SZ_X + G::SZ_U;
 };
 // The kernel's body for ONE tile shape (SH 0 / 1); `smem` = the block's LDS (fused2_warp_lds<R, SH, SUM>::N floats), `region`:
 // fused_tile.  The __global__ wrapper below owns the LDS and, in a mixed launch, picks the shape per block.
 // BIG: the three-component field arrays span >= 2^32 bytes (e.g. 512 x 512 x 1400): their component / plane offsets no longer fit
 // the scalar-offset operand of ONE resource per array, so those accesses rebuild a resource from a 64-bit base per component and
-// plane (the PP_SOFF = 0 form); the scalar images (< 2^32 bytes each: checked on the host) keep theirs.
+// plane (the form without a scalar offset); the scalar images (< 2^32 bytes each: checked on the host) keep theirs.
 template <int R, int SH, bool UNROLL, bool SUM, bool NT, bool MASK, bool BIG = false>
 __device__ __forceinline__ void fused2_warp_body(const float* __restrict__ D, const float* __restrict__ Us, const float* __restrict__ M,
                                                  float* __restrict__ Dn, float* __restrict__ Mw, const fused_args& a,
@@ -755,8 +551,8 @@ __device__ __forceinline__ void fused2_warp_body(const float* __restrict__ D, co
                                                  const int region) {
   using G = strip_geom<R, SH, 0>;
   constexpr int NTH = G::NTH, TX = G::TX, TY = G::TY, W = 2 * R + 1;
-  constexpr bool XS = (PP_B_XSHFL != 0) && SUM;   // x pass in registers (wavefront shuffles), y-pass buffer double-buffered
-  constexpr bool SOFF_F = (PP_SOFF != 0) && !BIG, SOFF_S = (PP_SOFF != 0);   // scalar-offset addressing of field / scalar arrays
+  constexpr bool XS = SUM;   // x pass in registers (wavefront shuffles), y-pass buffer double-buffered
+  constexpr bool SOFF_F = !BIG;   // scalar-offset addressing of the field arrays (the scalar images always have it)
   static_assert(!(BIG && MASK), "the MASK instances keep whole arrays under 2^31 bytes");
   float* const s_x = smem;
   float* const s_u = smem + G::SZ_X;   // (XS: the second y-pass buffer)
@@ -778,8 +574,9 @@ __device__ __forceinline__ void fused2_warp_body(const float* __restrict__ D, co
   if constexpr (XS) {
     constexpr int RPW = strip_lanes<G>::RPW;
     // (strip rows by ROLE: three rows a wave for waves 0-5, two for wave 6, none for wave 7 -- the wave index is reversed in
-    // every other block of a CU's pair, as in kernel A, so that a SIMD hosts a heavy wave of one block and a light one of the other)
-    const int wrole = ((PP_B_FLIP != 0) && ((blockIdx.x >> 8) & 1u)) ? (NTH / 64 - 1) - (t >> 6) : (t >> 6);
+    // every other block of a CU's pair, so that a SIMD hosts a heavy wave of one block and a light one of the other: -1 % on
+    // kernel B; the same flip of kernel A's work roles measured no gain)
+    const int wrole = ((blockIdx.x >> 8) & 1u) ? (NTH / 64 - 1) - (t >> 6) : (t >> 6);
     const int lane = t & 63, riw = lane / G::SPR, sx = lane - riw * G::SPR;
     const int uy = wrole * RPW + riw;
     const bool valid = riw < RPW && uy < G::UH;
@@ -798,23 +595,19 @@ __device__ __forceinline__ void fused2_warp_body(const float* __restrict__ D, co
   const unsigned o_xy = ((unsigned)y * sy + (unsigned)x) * 4u;
   const pp_warp_dims wd{d.nx, d.ny, d.nz, sy * 4u, sz * 4u};
   const char* const rm = reinterpret_cast<const char*>(M);
-  const pp_rsrc r_dn = MASK ? pp_make_rsrc_masked(Dn) : pp_make_rsrc(Dn), r_mw = MASK ? pp_make_rsrc_masked(Mw) : pp_make_rsrc(Mw);   // one resource per output array (PP_SOFF)
+  const pp_rsrc r_dn = MASK ? pp_make_rsrc_masked(Dn) : pp_make_rsrc(Dn), r_mw = MASK ? pp_make_rsrc_masked(Mw) : pp_make_rsrc(Mw);   // one resource per output array
 
   const int zs = z0 - R;
   const int zo_last = (z0 + a.zchunk - 1 < d.nz - 1) ? z0 + a.zchunk - 1 : d.nz - 1;
   const int ze = zo_last + R;
   const int zhi = pp_clampi(ze, 0, d.nz - 1);
   const int nsteps = ze - zs + 1;
-  constexpr bool SYNC = (PP_SOFTSYNC != 0) && MASK;
-  pp_softsync ysync{};
-  if constexpr (SYNC) pp_softsync_init(ysync, a, a.sync_other);
-  constexpr bool PRIO = (PP_PAIRPRIO != 0) && MASK;
   pp_pairprio yprio{};
-  if constexpr (PRIO) pp_pairprio_init(yprio, a, a.sync_other);
+  if constexpr (MASK) pp_pairprio_init(yprio, a, a.sync_other);
 
   float4 dl[SUM ? 1 : 3][G::NSL], ul[3][G::NSL];   // raw D and U strips of the plane about to be published
   // (ALL: every lane loads -- a lane without a strip re-reads strip 0 of the tile, whose address pp_strip_setup gave it -- so
-  // that no divergent branch surrounds the loads of a steady step: inside one, the compiler copies the loaded registers at
+  // that no divergent branch surrounds the loads of a MASK step: inside one, the compiler copies the loaded registers at
   // once and waits for the load it has just issued)
   auto load_plane = [&](int zc, auto all_tag) {
     constexpr bool ALL = decltype(all_tag)::value;
@@ -825,13 +618,8 @@ __device__ __forceinline__ void fused2_warp_body(const float* __restrict__ D, co
 #pragma unroll
       for (int i = 0; i < G::NSL; ++i)
         if (ALL || (i + 1) * NTH <= G::NS || st[i].slot >= 0) {
-#ifdef PP_ABL_NOLOAD
-          if constexpr (!SUM) dl[c][i] = make_float4((float)st[i].goff * 1e-9f + (float)zc, 0.f, 1.f, 2.f);
-          ul[c][i] = make_float4((float)st[i].goff * 1e-9f, 1.f, 0.f, 3.f);
-#else
           if constexpr (!SUM) dl[c][i] = pp_gld4(pd, st[i].goff);
           ul[c][i] = pp_gld4(pu, st[i].goff);
-#endif
         }
     }
   };
@@ -863,15 +651,15 @@ __device__ __forceinline__ void fused2_warp_body(const float* __restrict__ D, co
   // prologue: first plane through publish + x pass, second plane in flight
   {
     const int zc0 = pp_clampi(zs, 0, d.nz - 1);
-    load_plane(zc0, pp_steady<false>{});
+    load_plane(zc0, std::false_type{});
     if constexpr (XS) {
       const float4 s3[3] = {ul[0][0], ul[1][0], ul[2][0]};
       fused2_xpass_shfl<R, G>(s3, st[0].jm, xs_out, xs_off, s_x, a.wx);
-      if (zc0 < zhi) load_plane(zc0 + 1, pp_steady<false>{});
+      if (zc0 < zhi) load_plane(zc0 + 1, std::false_type{});
       __syncthreads();
     } else {
       publish();
-      if (zc0 < zhi) load_plane(zc0 + 1, pp_steady<false>{});
+      if (zc0 < zhi) load_plane(zc0 + 1, std::false_type{});
       __syncthreads();
       fused2_xpass_strips<R, G>(s_u, s_x, a.wx, xsrc, xdst);
       __syncthreads();
@@ -879,31 +667,20 @@ __device__ __forceinline__ void fused2_warp_body(const float* __restrict__ D, co
   }
   int ybuf = 0;   // XS: the buffer that holds the current plane's x-pass result
 
-  const bool trace_on = (rank == (unsigned)(a.gx * (a.gy / 2) + a.gx / 2));   // (PP_TRACE builds: an interior tile, first z-chunk)
-  (void)trace_on;
-  // steady steps (fused2_plane_loop3): planes zi - 1, zi, zi + 1, zi + 2 exist, zi - R is an output plane of this chunk and
-  // the tile lies inside the volume with even rows, so every lane stores pairs
-  const bool tile_full = (tx0 + TX <= d.nx) && (ty0 + TY <= d.ny) && pair_ok;
-  const int s_lo = (2 * R > 1 - zs) ? 2 * R : 1 - zs;
-  const int s_hi = tile_full ? zhi - 1 - zs : 0;
-  auto step = [&](int n, auto phase_tag, auto steady_tag) {
+  auto step = [&](int n, auto phase_tag) {
     constexpr int P = decltype(phase_tag)::value;
-    constexpr bool ST = decltype(steady_tag)::value;
     const int zi = zs + n;
-    const int cur = ST ? zi : pp_clampi(zi, 0, d.nz - 1);
-    const bool fresh_cur = ST || (n == 0) || (cur != pp_clampi(zi - 1, 0, d.nz - 1));
-    const int nxt = ST ? zi + 1 : pp_clampi(zi + 1, 0, d.nz - 1);
-    const bool fresh_next = ST || ((n + 1 < nsteps) && (nxt != cur));
-    PP_TRACE_MARK(trace_on, 1, n, 0);
-    PP_DRIFT_MARK(1, n, nsteps);
-    if constexpr (SYNC) pp_softsync_peek(ysync);
-    if constexpr (PRIO) pp_pairprio_peek(yprio);
+    const int cur = pp_clampi(zi, 0, d.nz - 1);
+    const bool fresh_cur = (n == 0) || (cur != pp_clampi(zi - 1, 0, d.nz - 1));
+    const int nxt = pp_clampi(zi + 1, 0, d.nz - 1);
+    const bool fresh_next = (n + 1 < nsteps) && (nxt != cur);
+    if constexpr (MASK) pp_pairprio_peek(yprio);
     // ---- interval 1: y pass of plane `cur` (reads s_x) | publish plane `nxt` (writes s_u) ----
     if (fresh_cur) {
 #pragma unroll
       for (int c = 0; c < 3; ++c) fused2_ypass_strips<R, G>(XS ? smem + ybuf * G::SZ_X : s_x, c, yb, a.wy, v[c]);
     }
-    // Round 4 (PP_B_XLATE): the x pass of plane `nxt` -- the consumer of the strips -- runs at the END of the interval, and the
+    // XS: the x pass of plane `nxt` -- the consumer of the strips -- runs at the END of the interval, and the
     // next strips are requested right behind it: a strip load then has a whole plane step to arrive (it used to be issued
     // two thirds into a step and consumed at the top of the next one, ~1.4 us later: less than the loaded HBM latency).
     auto xpass_next = [&]() {
@@ -916,70 +693,43 @@ __device__ __forceinline__ void fused2_warp_body(const float* __restrict__ D, co
         if (fresh_next) publish();
       }
     };
-    constexpr bool XLATE = XS && (PP_B_XLATE != 0);
-    if constexpr (!XLATE) xpass_next();
+    if constexpr (!XS) xpass_next();
     float dn[3][2];
     fused2_ring<R, P>(rg, v, a.wz, dn);
     const int zo = zi - R;
-    const bool emit = ST || ((zo >= z0) && (zo <= zo_last));
-    constexpr bool UNC = MASK || ST;   // memory instructions issued unconditionally (see MASK above the kernel)
+    const bool emit = (zo >= z0) && (zo <= zo_last);
     float mw0 = FLT_MAX, mw1 = FLT_MAX;
-#ifdef PP_ABL_NOGATHER
-    if (emit) {
-      mw0 = dn[0][0] + dn[1][0] * dn[2][0];
-      mw1 = dn[0][1] + dn[1][1] * dn[2][1];
-    }
-#else
-    // The 8 corner loads of the two samples are issued here and consumed after the barrier (PP_B_DEFER): their latency hides
-    // behind the strip loads, the field stores and the barrier instead of stalling the wave at once.  (UNC: also on steps
-    // that emit nothing -- the displacement is clamped, so the addresses are valid, and the result is never stored.)
+    // The 8 corner loads of the two samples are issued here and consumed after the barrier: their latency hides behind the
+    // strip loads, the field stores and the barrier instead of stalling the wave at once.  (MASK: also on steps that emit
+    // nothing -- the displacement is clamped, so the addresses are valid, and the result is never stored.)
     pp_warp_pending g0, g1;
     bool wfast = false;   // (wave-uniform: the vote of fused2_warp_issue_pair)
-    if (UNC || emit) {
-#if PP_B_VOTE
+    if (MASK || emit) {
       wfast = fused2_warp_issue_pair(rm, wd, x, y, zo, dn[0][0] * sc.ix, dn[1][0] * sc.iy, dn[2][0] * sc.iz, dn[0][1] * sc.ix,
-                                     dn[1][1] * sc.iy, dn[2][1] * sc.iz, ST || out_ok, ST || (out_ok && (x + 1 < d.nx)), g0, g1);
-#else
-      fused2_warp_issue(rm, wd, x, dn[0][0] * sc.ix, y, dn[1][0] * sc.iy, zo, dn[2][0] * sc.iz, ST || out_ok, g0);
-      fused2_warp_issue(rm, wd, x + 1, dn[0][1] * sc.ix, y, dn[1][1] * sc.iy, zo, dn[2][1] * sc.iz, ST || (out_ok && (x + 1 < d.nx)), g1);
-#endif
-#if !PP_B_DEFER
-      if (wfast) {
-        mw0 = fused2_warp_finish_interior(g0);
-        mw1 = fused2_warp_finish_interior(g1);
-      } else {
-        mw0 = fused2_warp_finish(g0);
-        mw1 = fused2_warp_finish(g1);
-      }
-#endif
+                                     dn[1][1] * sc.iy, dn[2][1] * sc.iz, out_ok, out_ok && (x + 1 < d.nx), g0, g1);
     }
-#endif
-    // the plane after `nxt` goes in flight behind the gathers.  UNC pins the issue order gathers -> strip loads -> field
+    // the plane after `nxt` goes in flight behind the gathers.  MASK pins the issue order gathers -> strip loads -> field
     // stores: vmcnt retires in issue order, so the wait for the gathers must not have the younger HBM loads ahead of it.
     auto load_next = [&]() {
-      if constexpr (UNC) {
+      if constexpr (MASK) {
         __builtin_amdgcn_sched_barrier(0);
         // (steps that would not load re-read the plane the strips already hold: min(nxt + 1, zhi))
-        const int zl = ST ? nxt + 1 : (nxt + 1 < zhi ? nxt + 1 : zhi);
-        load_plane(zl, pp_steady<(G::NSL == 1)>{});
+        const int zl = nxt + 1 < zhi ? nxt + 1 : zhi;
+        load_plane(zl, std::bool_constant<G::NSL == 1>{});
         __builtin_amdgcn_sched_barrier(0);
       } else {
-        if (fresh_next && nxt < zhi) load_plane(nxt + 1, pp_steady<false>{});
+        if (fresh_next && nxt < zhi) load_plane(nxt + 1, std::false_type{});
       }
     };
-    if constexpr (!XLATE) load_next();
-    const int zoc = (UNC && !ST) ? pp_clampi(zo, z0, zo_last) : zo;   // (a plane of this chunk also when nothing is stored)
+    if constexpr (!XS) load_next();
+    const int zoc = MASK ? pp_clampi(zo, z0, zo_last) : zo;   // (a plane of this chunk also when nothing is stored)
     const size_t po = (size_t)zoc * sz;
     const unsigned po4 = (unsigned)zoc * sz * 4u, N4 = (unsigned)N * 4u;   // (3 N * 4 < 2^32: checked on the host)
-#ifdef PP_ABL_NOSTORE
-    const bool do_store = emit && out_ok && dn[0][0] == 3.21e-29f && dn[1][1] == 1e-31f && dn[2][0] == 7e-33f && dn[0][1] == 2e-30f && dn[1][0] == 3e-30f && dn[2][1] == 4e-30f;
-#else
-    const bool do_store = ST || (emit && out_ok);
-#endif
-    // UNC: one store form (even rows), the lane mask in the offset
+    const bool do_store = emit && out_ok;
+    // MASK: one store form (even rows), the lane mask in the offset
     const unsigned o_st = (MASK && !do_store) ? PP_OOB : o_xy;
     auto store_field = [&]() {
-      if (UNC || pair_ok) {
+      if (MASK || pair_ok) {
 #pragma unroll
         for (int c = 0; c < 3; ++c) {
           if constexpr (SOFF_F) pp_bst2ss<NT>(r_dn, o_st, c * N4 + po4, dn[c][0], dn[c][1]);
@@ -997,35 +747,25 @@ __device__ __forceinline__ void fused2_warp_body(const float* __restrict__ D, co
       }
     };
     auto store_image = [&]() {
-      if (UNC || pair_ok) {
-        if constexpr (SOFF_S) pp_bst2ss<NT>(r_mw, o_st, po4, mw0, mw1);
-        else pp_bst2s<NT>(pp_make_rsrc(Mw + po), o_st, mw0, mw1);
+      if (MASK || pair_ok) {
+        pp_bst2ss<NT>(r_mw, o_st, po4, mw0, mw1);
       } else if (x + 1 < d.nx) {
         pp_gst2(reinterpret_cast<char*>(Mw + po), o_xy, mw0, mw1);
       } else {
-        if constexpr (SOFF_S) pp_bsts(r_mw, o_xy, po4, mw0);
-        else pp_bst(pp_make_rsrc(Mw + po), o_xy, mw0);
+        pp_bsts(r_mw, o_xy, po4, mw0);
       }
     };
-    if (UNC || do_store) {
-      store_field();
-#if !PP_B_DEFER || defined(PP_ABL_NOGATHER)
-      store_image();
-#endif
-    }
-    if constexpr (XLATE) {
-      if constexpr (UNC) __builtin_amdgcn_sched_barrier(0);
+    if (MASK || do_store) store_field();
+    if constexpr (XS) {
+      if constexpr (MASK) __builtin_amdgcn_sched_barrier(0);
       xpass_next();
       load_next();
     }
-    if constexpr (UNC) __builtin_amdgcn_sched_barrier(0);
+    if constexpr (MASK) __builtin_amdgcn_sched_barrier(0);
     // ---- interval 2: x pass of plane `nxt` (XS: already done above; one barrier hands the buffers over) ----
-    PP_TRACE_MARK(trace_on, 1, n, 1);
-    if constexpr (SYNC) pp_softsync_step(ysync, n);
-    if constexpr (PRIO) pp_pairprio_step(yprio, n);
+    if constexpr (MASK) pp_pairprio_step(yprio, n);
     if (fresh_next) {
       __syncthreads();
-      PP_TRACE_MARK(trace_on, 1, n, 2);
       if constexpr (XS) {
         ybuf ^= 1;
       } else {
@@ -1033,11 +773,8 @@ __device__ __forceinline__ void fused2_warp_body(const float* __restrict__ D, co
         __syncthreads();
       }
     }
-#if PP_B_DEFER && !defined(PP_ABL_NOGATHER)
-#if PP_B_FINISH_AFTER_BARRIER
-    if constexpr (UNC) __builtin_amdgcn_sched_barrier(0);   // (keep the gathers' wait behind the barrier, where the source has it)
-#endif
-    if (UNC || emit) {
+    if constexpr (MASK) __builtin_amdgcn_sched_barrier(0);   // (keep the gathers' wait behind the barrier, where the source has it)
+    if (MASK || emit) {
       if (wfast) {
         mw0 = fused2_warp_finish_interior(g0);
         mw1 = fused2_warp_finish_interior(g1);
@@ -1046,26 +783,16 @@ __device__ __forceinline__ void fused2_warp_body(const float* __restrict__ D, co
         mw1 = fused2_warp_finish(g1);
       }
     }
-    if (UNC || do_store) store_image();
-#endif
-    PP_TRACE_MARK(trace_on, 1, n, 3);
+    if (MASK || do_store) store_image();
   };
-#if PP_STEADY
-  fused2_plane_loop3<R, UNROLL>(step, nsteps, s_lo, s_hi);
-#else
-  (void)s_lo;
-  (void)s_hi;
-  auto step_general = [&](int n, auto phase_tag) { step(n, phase_tag, pp_steady<false>{}); };
-  fused2_plane_loop<R, UNROLL>(step_general, nsteps);
-#endif
-  if constexpr (SYNC) pp_softsync_finish(ysync);
-  if constexpr (PRIO) pp_pairprio_finish(yprio);
+  fused2_plane_loop<R, UNROLL>(step, nsteps);
+  if constexpr (MASK) pp_pairprio_finish(yprio);
 }
 
 // SH 0 / 1: every tile of that shape.  SH 2: tiles of both shapes in one launch (fused_args: gx2 > 0) -- 64 x 16 wherever a
 // whole 64-wide tile fits, 32 x 32 over the remaining columns -- with the LDS of the larger carve.
 template <int R, int SH, bool UNROLL, bool SUM, bool NT, bool MASK, bool BIG = false>
-__global__ void __launch_bounds__(512, PP_GEN2_WAVES) k_fused2_add_smooth_warp(const float* __restrict__ D, const float* __restrict__ Us,
+__global__ void __launch_bounds__(512, GEN2_WAVES) k_fused2_add_smooth_warp(const float* __restrict__ D, const float* __restrict__ Us,
                                                                             const float* __restrict__ M, float* __restrict__ Dn,
                                                                             float* __restrict__ Mw, fused_args a, pp_warp_scale sc,
                                                                             const int* __restrict__ halt) {
@@ -1110,17 +837,6 @@ __device__ __forceinline__ float pp_esm_axis_plain2(pp_v2f lo /* (m, f) below */
   return fg + wg;
 }
 
-// Kernel A's z window element: the (warped, fixed) values of one owned voxel on one plane -- a register PAIR (PP_A_ZPAIRS: the z
-// gradient is then packed like the x and y ones and the window rotates by 64-bit moves) or two independent registers.
-#ifndef PP_A_ZPAIRS
-#define PP_A_ZPAIRS 0
-#endif
-#if PP_A_ZPAIRS
-#define PP_ZWIN(name, n) pp_v2f name[n]
-#else
-#define PP_ZWIN(name, n) float name[n][2]
-#endif
-
 // One axis of the gradient where both neighbours exist and neither warped value is the sentinel: pp_esm_axis /
 // pp_esm_axis_data with `up`, `um` true and the first / last-index factor h -- the same two statements, so the same roundings.
 __device__ __forceinline__ float pp_esm_axis_plain(float fm, float fp, float mm, float mp, float inv_sp) {
@@ -1136,7 +852,7 @@ __device__ __forceinline__ float pp_esm_axis_plain(float fm, float fp, float mm,
 // LDS floats of kernel A for one tile shape: the packed image tile, the smoothing input, the x-pass tile
 template <int R, int SH>
 struct fused2_force_lds {
-  using G = fused_geom<R, 2, SH>;
+  using G = fused_geom<R, SH>;
   static constexpr int SZ_IMG2 = (2 * G::MH * G::MWP + 3) / 4 * 4;   // packed (moving, fixed) tile, floats
   static constexpr int SZ_U = G::SZ_U;
   static constexpr int SZ_XT = 3 * G::UH * fused2_xtile<SH>::XP;     // x-pass tile (>= G::SZ_X: the row pitch may be padded)
@@ -1148,10 +864,10 @@ __device__ __forceinline__ void fused2_force_body(const float* __restrict__ F, c
                                                   double* __restrict__ partials, pp_dev_stats* __restrict__ st,
                                                   const double* __restrict__ prev, int nprev, double max_rms, float2* const s_mf,
                                                   float* const s_u, float* const s_x, const int region) {
-  using G = fused_geom<R, 2, SH>;
+  using G = fused_geom<R, SH>;
   constexpr int NTH = G::NTH, TX = G::TX, TY = G::TY, W = 2 * R + 1;
   constexpr int NXI = (3 * G::XI + NTH - 1) / NTH;
-  constexpr bool SOFF_F = (PP_SOFF != 0) && !BIG, SOFF_S = (PP_SOFF != 0);
+  constexpr bool SOFF_F = !BIG;   // (as in fused2_warp_body)
   static_assert(!(BIG && MASK), "the MASK instances keep whole arrays under 2^31 bytes");
   float* const smem = s_u;   // (the reduction scratch of the prologue: 3 * 8 doubles)
   if (st->halt) return;   // (written by an earlier launch)
@@ -1196,17 +912,10 @@ __device__ __forceinline__ void fused2_force_body(const float* __restrict__ F, c
 
   const pp_dims d = a.d;
   const int t = threadIdx.x;
-  // Work that is not tied to an output voxel -- the ESM update of the halo'd smoothing input (22 wave-rounds over 8 waves: 3 3 3
-  // 3 3 3 2 2), the image tile's border ring (waves 0-2) and the x-pass items (2 2 2 2 2 2 2 1) -- is dealt by ROLE: the wave
-  // index reversed in every other block of a CU's pair (blocks j and j + 32 of an XCD's run share a CU when the dispatcher
-  // fills the CUs round-robin), so that the SIMD that hosts the heavy waves 0 / 4 of one block hosts the light waves 7 / 3 of
-  // the other: 11 + 11 + 11 + 11 ESM rounds per SIMD and plane instead of 12 + 12 + 10 + 10.  The lane keeps its place (the
-  // x pass's conflict-free order is by lane).  Same arithmetic by another thread: fields bit-identical.
-  const int tr = ((PP_A_FLIP != 0) && ((blockIdx.x >> 8) & 1u)) ? (((NTH / 64 - 1) - (t >> 6)) << 6 | (t & 63)) : t;
   const int cx = t % G::LX, cy = t / G::LX;
   const unsigned sy = (unsigned)a.px, sz = (unsigned)a.px * d.ny;
   const size_t N = (size_t)sz * d.nz;
-  const pp_rsrc r_f = pp_make_rsrc(F), r_mw = pp_make_rsrc(Mw);   // (PP_SOFF)
+  const pp_rsrc r_f = pp_make_rsrc(F), r_mw = pp_make_rsrc(Mw);   // (scalar-offset addressing, see pp_blds)
   const pp_rsrc r_d = pp_make_rsrc(D), r_us = MASK ? pp_make_rsrc_masked(Us) : pp_make_rsrc(Us);
 
   // Owned smoothing-input voxels.  Image values are fetched at the clamped position, so out-of-volume halo slots
@@ -1214,17 +923,16 @@ __device__ __forceinline__ void fused2_force_body(const float* __restrict__ F, c
   unsigned slots[G::KU];  // read slot of the clamped position, minus one row | write slot << 16   (in s_mf)
   unsigned uflag[G::KU];  // slot in s_u | flags << 16
   unsigned own_g[G::KU];  // in-plane BYTE offset of the clamped position
-  // z window of the image pair at the owned voxels, kept as (warped, fixed) PAIRS: the z gradient is then the packed form of
-  // the x and y ones (pp_esm_axis_plain2), and the window rotates by 64-bit moves
-  PP_ZWIN(wprev, G::KU);
-  PP_ZWIN(wcur, G::KU);
-  PP_ZWIN(wnext, G::KU);
+  // z window of the image pair at the owned voxels: [k][0] warped, [k][1] fixed
+  float wprev[G::KU][2];
+  float wcur[G::KU][2];
+  float wnext[G::KU][2];
   // (border rules are carried by data -- a slot outside the volume publishes the sentinel in its warped-image half, the
   // fixed-gradient factor is 0 on a first/last index -- and both are derived from the flag bits where they are used: only
   // blocks on the volume's x/y border ever need them, and nine registers held them for every block.)
 #pragma unroll
   for (int k = 0; k < G::KU; ++k) {
-    const int e = tr + k * NTH;
+    const int e = t + k * NTH;
     const int ee = e < G::NU ? e : 0;
     const int uy = ee / G::UW, ux = ee - uy * G::UW;
     const int xg = tx0 - R + ux, yg = ty0 - R + uy;
@@ -1249,18 +957,18 @@ __device__ __forceinline__ void fused2_force_body(const float* __restrict__ F, c
   int brd_w = -1;
   unsigned brd_g = 0;
   float brd_oov = -FLT_MAX;
-  if (tr < G::NB) {
+  if (t < G::NB) {
     int my, mx;
-    if (tr < G::MW) { my = 0; mx = tr; }
-    else if (tr < 2 * G::MW) { my = G::MH - 1; mx = tr - G::MW; }
-    else { const int q = tr - 2 * G::MW; my = 1 + q / 2; mx = (q & 1) ? G::MW - 1 : 0; }
+    if (t < G::MW) { my = 0; mx = t; }
+    else if (t < 2 * G::MW) { my = G::MH - 1; mx = t - G::MW; }
+    else { const int q = t - 2 * G::MW; my = 1 + q / 2; mx = (q & 1) ? G::MW - 1 : 0; }
     const int xc = pp_clampi(tx0 - R - 1 + mx, 0, d.nx - 1), yc = pp_clampi(ty0 - R - 1 + my, 0, d.ny - 1);
     if (xc != tx0 - R - 1 + mx || yc != ty0 - R - 1 + my) brd_oov = FLT_MAX;
     brd_w = my * G::MWP + mx;
     brd_g = ((unsigned)yc * sy + (unsigned)xc) * 4u;
   }
   int xsrc[NXI], xdst[NXI];
-  fused2_xpass_setup<R, SH, NXI>(tr, xsrc, xdst);
+  fused2_xpass_setup<R, SH, NXI>(t, xsrc, xdst);
   const int yb = cy * fused2_xtile<SH>::XP + 2 * cx;
   const int x = tx0 + 2 * cx, y = ty0 + cy;
   const bool out_ok = (y < d.ny) && (x < d.nx);
@@ -1271,15 +979,11 @@ __device__ __forceinline__ void fused2_force_body(const float* __restrict__ F, c
   const int zo_last = (z0 + a.zchunk - 1 < d.nz - 1) ? z0 + a.zchunk - 1 : d.nz - 1;
   const int ze = zo_last + R;
   const int nsteps = ze - zs + 1;
-  constexpr bool SYNC = (PP_SOFTSYNC != 0) && MASK;
-  pp_softsync ysync{};
-  if constexpr (SYNC) pp_softsync_init(ysync, a, a.sync_other);
-  constexpr bool PRIO = (PP_PAIRPRIO != 0) && MASK;
   pp_pairprio yprio{};
-  if constexpr (PRIO) pp_pairprio_init(yprio, a, a.sync_other);
+  if constexpr (MASK) pp_pairprio_init(yprio, a, a.sync_other);
 
   float bm = 0.0f, bf = 0.0f;          // border ring values of the plane about to be published
-  PP_ZWIN(win_, G::KU);                // plane two ahead of the window centre, in flight
+  float win_[G::KU][2];                // plane two ahead of the window centre, in flight
   float bm_n = 0.0f, bf_n = 0.0f;
   float a_ssd = 0.0f, a_ssc = 0.0f, a_n = 0.0f;   // <= ~40 terms per thread: fp32 is exact enough, folded in fp64 below
 
@@ -1293,48 +997,22 @@ __device__ __forceinline__ void fused2_force_body(const float* __restrict__ F, c
     if (brd_w >= 0) s_mf[brd_w] = make_float2(fmaxf(bm, brd_oov), bf);
   };
   auto prefetch = [&](int zc) {   // own voxels of plane zc + 2, border ring of plane zc + 1
-#ifdef PP_ABL_A_NOLOAD
-    {   // (measurement builds: no image loads)
-#pragma unroll
-      for (int k = 0; k < G::KU; ++k) {
-        win_[k][0] = (float)own_g[k] * 1e-3f + (float)zc;
-        win_[k][1] = (float)own_g[k] * 2e-3f - (float)zc;
-      }
-      bm_n = 1.0f;
-      bf_n = 2.0f;
-      return;
-    }
-#endif
     const size_t p2 = (size_t)pp_clampi(zc + 2, 0, d.nz - 1) * sz, p1 = (size_t)pp_clampi(zc + 1, 0, d.nz - 1) * sz;
-    if constexpr (SOFF_S) {
-      const unsigned s2 = (unsigned)p2 * 4u, s1 = (unsigned)p1 * 4u;
+    const unsigned s2 = (unsigned)p2 * 4u, s1 = (unsigned)p1 * 4u;
 #pragma unroll
-      for (int k = 0; k < G::KU; ++k) {
-        win_[k][0] = pp_blds(r_mw, own_g[k], s2);
-        win_[k][1] = pp_blds(r_f, own_g[k], s2);
-      }
-      if (MASK || brd_w >= 0) {   // (MASK: lanes without a ring element read voxel 0 of the plane)
-        bm_n = pp_blds(r_mw, brd_g, s1);
-        bf_n = pp_blds(r_f, brd_g, s1);
-      }
-    } else {
-      const pp_rsrc rm2 = pp_make_rsrc(Mw + p2), rf2 = pp_make_rsrc(F + p2);
-#pragma unroll
-      for (int k = 0; k < G::KU; ++k) {
-        win_[k][0] = pp_bld(rm2, own_g[k]);
-        win_[k][1] = pp_bld(rf2, own_g[k]);
-      }
-      if (MASK || brd_w >= 0) {
-        bm_n = pp_bld(pp_make_rsrc(Mw + p1), brd_g);
-        bf_n = pp_bld(pp_make_rsrc(F + p1), brd_g);
-      }
+    for (int k = 0; k < G::KU; ++k) {
+      win_[k][0] = pp_blds(r_mw, own_g[k], s2);
+      win_[k][1] = pp_blds(r_f, own_g[k], s2);
+    }
+    if (MASK || brd_w >= 0) {   // (MASK: lanes without a ring element read voxel 0 of the plane)
+      bm_n = pp_blds(r_mw, brd_g, s1);
+      bf_n = pp_blds(r_f, brd_g, s1);
     }
   };
-  auto esm = [&](int zc, auto interior_tag) __attribute__((always_inline)) {   // update at every smoothing-input voxel of plane zc (the window centre) -> s_u, then rotate
-    constexpr bool ZIN = decltype(interior_tag)::value;   // 0 < zc < nz - 1 known at compile time (steady steps)
+  auto esm = [&](int zc) __attribute__((always_inline)) {   // update at every smoothing-input voxel of plane zc (the window centre) -> s_u, then rotate
     const bool count_plane = (zc >= z0 && zc <= zo_last);
-    const bool zlo_b = ZIN ? false : (zc == 0), zhi_b = ZIN ? false : (zc == d.nz - 1);
-    if constexpr ((PP_A_VOTE != 0) && MASK) {   // (the branchy instances have no registers left for it: 6 spills, +11 % measured)
+    const bool zlo_b = (zc == 0), zhi_b = (zc == d.nz - 1);
+    if constexpr (MASK) {   // (the branchy instances have no registers left for it: 6 spills, +11 % measured)
     // Round 4: one wavefront vote per round.  Where no lane of the wavefront sits on a first / last index and none of its seven
     // warped-image values is the sentinel -- everywhere but next to the volume's border and to voxels the warp mapped outside
     // the moving image -- ITK's case analysis selects the central difference on every axis, and the three gradients are five
@@ -1355,18 +1033,9 @@ __device__ __forceinline__ void fused2_force_body(const float* __restrict__ F, c
         const bool plain = !valid || (((flb & (F_XLO | F_XHI | F_YLO | F_YHI)) == 0u) & (mmax < FLT_MAX));
         pp_esm_out o;
         if (z_inner && !__any(!plain)) {
-#if PP_A_ESM_PAIRS
           const float gx = pp_esm_axis_plain2(xm2, xp2, K.ix);
           const float gy = pp_esm_axis_plain2(ym2, yp2, K.iy);
-#else
-          const float gx = pp_esm_axis_plain(xm.y, xp.y, xm.x, xp.x, K.ix);
-          const float gy = pp_esm_axis_plain(ym.y, yp.y, ym.x, yp.x, K.iy);
-#endif
-#if PP_A_ESM_PAIRS && PP_A_ZPAIRS
-          const float gz = pp_esm_axis_plain2(wprev[k], wnext[k], K.iz);
-#else
           const float gz = pp_esm_axis_plain(wprev[k][1], wnext[k][1], wprev[k][0], wnext[k][0], K.iz);
-#endif
           o = pp_esm_voxel<true>(K, wcur[k][1], wcur[k][0], gx, gy, gz);
         } else {
           const float hfx = (flb & (F_XLO | F_XHI)) ? 0.0f : 0.5f * K.ix, hfy = (flb & (F_YLO | F_YHI)) ? 0.0f : 0.5f * K.iy;
@@ -1415,14 +1084,8 @@ __device__ __forceinline__ void fused2_force_body(const float* __restrict__ F, c
     }
 #pragma unroll
     for (int k = 0; k < G::KU; ++k) {
-#if PP_A_ZPAIRS
-      wprev[k] = wcur[k];
-      wcur[k] = wnext[k];
-      wnext[k] = win_[k];
-#else
       wprev[k][0] = wcur[k][0]; wcur[k][0] = wnext[k][0]; wnext[k][0] = win_[k][0];
       wprev[k][1] = wcur[k][1]; wcur[k][1] = wnext[k][1]; wnext[k][1] = win_[k][1];
-#endif
     }
     bm = bm_n;
     bf = bf_n;
@@ -1440,7 +1103,7 @@ __device__ __forceinline__ void fused2_force_body(const float* __restrict__ F, c
   float2 dsum[SUM ? 3 : 1];
   const bool dzero = (nprev == 0);   // (wave-uniform; see the adds in the plane step)
   const unsigned o_xy1 = (x + 1 < d.nx) ? o_xy + 4u : o_xy;
-  auto load_dsum = [&](int zo, auto always_tag) {
+  auto load_dsum = [&](int zo) {
     if constexpr (MASK) {
       // One 8-byte load per component (rows are even, so the pair is aligned) on every step: a plane of this chunk, lanes
       // outside the volume read voxel 0 of it.  (A global load through the array's base: hipcc 7.2 lowers
@@ -1449,12 +1112,8 @@ __device__ __forceinline__ void fused2_force_body(const float* __restrict__ F, c
       const unsigned po = (unsigned)pp_clampi(zo, z0, zo_last) * sz;
       const unsigned o_ld = out_ok ? o_xy : 0u;
 #pragma unroll
-#ifdef PP_ABL_A_NOLOAD
-      for (int c = 0; c < (SUM ? 3 : 1); ++c) dsum[c] = make_float2((float)(o_ld + po) * 1e-6f, (float)c);
-#else
       for (int c = 0; c < (SUM ? 3 : 1); ++c) dsum[c] = pp_gld2(reinterpret_cast<const char*>(D), o_ld + ((unsigned)c * (unsigned)N + po) * 4u);
-#endif
-    } else if (decltype(always_tag)::value || (zo >= z0 && zo <= zo_last && out_ok)) {
+    } else if (zo >= z0 && zo <= zo_last && out_ok) {
       const size_t po = (size_t)zo * sz;
 #pragma unroll
       for (int c = 0; c < (SUM ? 3 : 1); ++c) {   // two 4-byte buffer loads: no alignment case, no branch (x + 1 == nx re-reads x)
@@ -1490,52 +1149,37 @@ __device__ __forceinline__ void fused2_force_body(const float* __restrict__ F, c
     publish();
     prefetch(zc0);
     __syncthreads();
-    esm(zc0, pp_steady<false>{});
+    esm(zc0);
     {   // step 0's image loads (see the end of the plane step)
       const int n1 = pp_clampi(zs + 1, 0, d.nz - 1);
       if (nsteps > 1 && n1 != zc0) prefetch(n1);
     }
-    if constexpr (SUM) load_dsum(zs - R, pp_steady<false>{});
+    if constexpr (SUM) load_dsum(zs - R);
     __syncthreads();
   }
 
-  const bool trace_on = (rank == (unsigned)(a.gx * (a.gy / 2) + a.gx / 2));   // (PP_TRACE builds: an interior tile, first z-chunk)
-  (void)trace_on;
-  // steady steps (fused2_plane_loop3): planes zi - 1 .. zi + 2 exist and zi + 1 is not the last one (no z-border rule in the
-  // update of plane zi + 1), zi - R and zi - R + 1 are output planes of this chunk, and the tile lies inside the volume with
-  // even rows, so every lane loads D and stores pairs
-  const bool tile_full = (tx0 + TX <= d.nx) && (ty0 + TY <= d.ny) && pair_ok;
-  const int s_lo = (2 * R > 1 - zs) ? 2 * R : 1 - zs;
-  const int s_hi = tile_full ? ((d.nz - 3 < ze - 2) ? d.nz - 3 : ze - 2) - zs + 1 : 0;
-  auto step = [&](int n, auto phase_tag, auto steady_tag) {
+  auto step = [&](int n, auto phase_tag, auto) {
     constexpr int P = decltype(phase_tag)::value;
-    constexpr bool ST = decltype(steady_tag)::value;
     const int zi = zs + n;
-    const int cur = ST ? zi : pp_clampi(zi, 0, d.nz - 1);
-    const bool fresh_cur = ST || (n == 0) || (cur != pp_clampi(zi - 1, 0, d.nz - 1));
-    const int nxt = ST ? zi + 1 : pp_clampi(zi + 1, 0, d.nz - 1);
-    const bool fresh_next = ST || ((n + 1 < nsteps) && (nxt != cur));
+    const int cur = pp_clampi(zi, 0, d.nz - 1);
+    const bool fresh_cur = (n == 0) || (cur != pp_clampi(zi - 1, 0, d.nz - 1));
+    const int nxt = pp_clampi(zi + 1, 0, d.nz - 1);
+    const bool fresh_next = (n + 1 < nsteps) && (nxt != cur);
     const int zo = zi - R;
-    const bool emit = ST || ((zo >= z0) && (zo <= zo_last) && out_ok);
-    PP_TRACE_MARK(trace_on, 0, n, 0);
-    PP_DRIFT_MARK(0, n, nsteps);
-    if constexpr (SYNC) pp_softsync_peek(ysync);
-    if constexpr (PRIO) pp_pairprio_peek(yprio);
+    const bool emit = (zo >= z0) && (zo <= zo_last) && out_ok;
+    if constexpr (MASK) pp_pairprio_peek(yprio);
     // ---- interval 1: x pass of plane `cur` (s_u -> s_x) | publish the image tile of plane `nxt` ----
     if (fresh_next) publish();
     if (fresh_cur) fused2_xpass<R, NXI, 3 * G::XI>(s_u, s_x, a.wx, xsrc, xdst);
-    PP_TRACE_MARK(trace_on, 0, n, 1);
     if (fresh_cur || fresh_next) __syncthreads();
-    PP_TRACE_MARK(trace_on, 0, n, 2);
     // ---- interval 2: y pass of plane `cur` (s_x -> registers) | ESM update of plane `nxt` (s_mf -> s_u) ----
     if (fresh_cur) {
 #pragma unroll
       for (int c = 0; c < 3; ++c) fused2_ypass<R, SH>(s_x, c, yb, a.wy, v[c]);
     }
-    if (fresh_next) esm(nxt, steady_tag);
+    if (fresh_next) esm(nxt);
     float us[3][2];
     fused2_ring<R, P>(rg, v, a.wz, us);
-    constexpr bool UNC = MASK || ST;   // memory instructions issued unconditionally
     if constexpr (SUM) {
       // First iteration of an Execute (nprev == 0): the field is zero by definition and its buffer has NOT been cleared (an
       // 805 MB memset at 512 x 512 x 256) -- whatever the loads above returned is replaced by the zeros it stands for.
@@ -1544,7 +1188,7 @@ __device__ __forceinline__ void fused2_force_body(const float* __restrict__ F, c
         for (int c = 0; c < 3; ++c) dsum[c] = make_float2(0.0f, 0.0f);
       }
     }
-    if constexpr (UNC) {
+    if constexpr (MASK) {
       // all three adds before the first store: the adds wait for the D loads of the previous step, and a wait placed between
       // two stores also waits for the first store's acknowledgement (vmcnt retires in issue order).  One store form (even
       // rows); the lane mask -- inside the volume, an output plane of this chunk -- travels in the offset.
@@ -1556,12 +1200,8 @@ __device__ __forceinline__ void fused2_force_body(const float* __restrict__ F, c
         }
       }
       __builtin_amdgcn_sched_barrier(0);   // (the scheduler would sink each add to its store again)
-      const unsigned po4 = (unsigned)(ST ? zo : pp_clampi(zo, z0, zo_last)) * sz * 4u, N4 = (unsigned)N * 4u;
-#ifdef PP_ABL_A_NOSTORE
-      const unsigned o_st = PP_OOB;   // (measurement builds: every store dropped by the range check)
-#else
-      const unsigned o_st = (ST || emit) ? o_xy : PP_OOB;
-#endif
+      const unsigned po4 = (unsigned)pp_clampi(zo, z0, zo_last) * sz * 4u, N4 = (unsigned)N * 4u;
+      const unsigned o_st = emit ? o_xy : PP_OOB;
 #pragma unroll
       for (int c = 0; c < 3; ++c) pp_bst2ss<NT>(r_us, o_st, (unsigned)c * N4 + po4, us[c][0], us[c][1]);
       __builtin_amdgcn_sched_barrier(0);   // (the next step's loads go behind the stores)
@@ -1578,7 +1218,7 @@ __device__ __forceinline__ void fused2_force_body(const float* __restrict__ F, c
       for (int c = 0; c < 3; ++c) {
         if constexpr (SOFF_F) {
           const unsigned so = ((unsigned)c * (unsigned)N + (unsigned)po) * 4u;
-          if (ST || pair_ok) {
+          if (pair_ok) {
             pp_bst2ss<NT>(r_us, o_xy, so, us[c][0], us[c][1]);
           } else if (x + 1 < d.nx) {
             pp_gst2(reinterpret_cast<char*>(Us + c * N + po), o_xy, us[c][0], us[c][1]);
@@ -1600,26 +1240,18 @@ __device__ __forceinline__ void fused2_force_body(const float* __restrict__ F, c
     // The next step's loads go in flight here, behind this step's stores, so that no wait of this step has them
     // pending: the image planes are consumed by the next ESM pass, D (SUM) by the next stores.
     {
-      const int nxt2 = ST ? zi + 2 : pp_clampi(zi + 2, 0, d.nz - 1);
-      if (UNC || ((n + 2 < nsteps) && (nxt2 != nxt))) prefetch(nxt2);   // (UNC: a step that would not load re-reads the planes it holds)
+      const int nxt2 = pp_clampi(zi + 2, 0, d.nz - 1);
+      if (MASK || ((n + 2 < nsteps) && (nxt2 != nxt))) prefetch(nxt2);   // (MASK: a step that would not load re-reads the planes it holds)
     }
-    if constexpr (SUM) load_dsum(zo + 1, steady_tag);
-    PP_TRACE_MARK(trace_on, 0, n, 3);
-    if constexpr (SYNC) pp_softsync_step(ysync, n);
-    if constexpr (PRIO) pp_pairprio_step(yprio, n);
+    if constexpr (SUM) load_dsum(zo + 1);
+    if constexpr (MASK) pp_pairprio_step(yprio, n);
     if (fresh_cur || fresh_next) __syncthreads();
-    PP_TRACE_MARK(trace_on, 0, n, 4);
   };
-#if PP_A_STEADY
-  fused2_plane_loop3<R, UNROLL>(step, nsteps, s_lo, s_hi);
-#else
-  (void)s_lo;
-  (void)s_hi;
-  auto step_general = [&](int n, auto phase_tag) { step(n, phase_tag, pp_steady<false>{}); };
-  fused2_plane_loop<R, UNROLL>(step_general, nsteps);
-#endif
-  if constexpr (SYNC) pp_softsync_finish(ysync);
-  if constexpr (PRIO) pp_pairprio_finish(yprio);
+  // (Through this wrapper, not directly as in kernel B: a direct call makes the compiler order two commutative operands and two
+  // scalar registers of the setup differently, i.e. not the code that was measured.)
+  auto step_fwd = [&](int n, auto phase_tag) { step(n, phase_tag, std::false_type{}); };
+  fused2_plane_loop<R, UNROLL>(step_fwd, nsteps);
+  if constexpr (MASK) pp_pairprio_finish(yprio);
   double r_ssd = (double)a_ssd, r_ssc = (double)a_ssc, r_n = (double)a_n;
   pp_block_sum3_shfl<NTH>(r_ssd, r_ssc, r_n, reinterpret_cast<double*>(s_u));
   if (t == 0) {
@@ -1633,7 +1265,7 @@ __device__ __forceinline__ void fused2_force_body(const float* __restrict__ F, c
 // one ESM round above the update stores of the previous one -- as slices of one array it must keep them in order, and each
 // wave pays the LDS round trip once per round.)
 template <int R, int SH, bool UNROLL, bool SUM, bool NT, bool MASK, bool BIG = false>
-__global__ void __launch_bounds__(512, PP_GEN2_WAVES) k_fused2_force_smooth(const float* __restrict__ F, const float* __restrict__ Mw,
+__global__ void __launch_bounds__(512, GEN2_WAVES) k_fused2_force_smooth(const float* __restrict__ F, const float* __restrict__ Mw,
                                                                          const float* __restrict__ D, float* __restrict__ Us,
                                                                          fused_args a, pp_esm_consts K,
                                                                          double* __restrict__ partials, pp_dev_stats* __restrict__ st,

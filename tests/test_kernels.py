@@ -1006,7 +1006,7 @@ def test_fused_discrete_gaussian_equals_the_three_passes(backend, shape, monkeyp
 
 
 def test_fused_demons_pair_mix_visits_every_tile_once(backend, monkeypatch):
-    """PP_PAIR_MIX: the second block of a CU (XCD-run index j >= 32) takes its x-neighbour's tile.  Only launches with more
+    """Pair mix (fused_rank): the second block of a CU (XCD-run index j >= 32) takes its x-neighbour's tile.  Only launches with more
     than 32 tiles per XCD ever swap, which the other tests' volumes never reach: 512 x 544 x 2 has 8 x 34 = 272 tiles of
     64 x 16 (34 per XCD), so ranks 32 / 33 of every XCD trade places.  A tile computed twice or never shows at once: against
     the ORACLE (and the staged schedule), MASK instances forced (pair priority and the progress words included)."""

@@ -5,7 +5,7 @@
 # build: "main" (platipy_amd/csrc/libplatipy_hip.so), a name under tools/kbench/variants/ (tools/kbench/build_variants.sh name
 # "-DFLAGS" ...), or a path to a .so.  Each ":"-suffix is one env spec for that build (kbench applies and clears it per run).
 #   tools/kbench/ab.sh -r 3 r4 main noflip:PP_FUSED_GEN=2
-#   tools/kbench/ab.sh -s "341 341 171" -p 1.5,1.5,1.5 main syncaw:PP_FUSED_SYNC=0:PP_FUSED_SYNC=4
+#   tools/kbench/ab.sh -s "341 341 171" -p 1.5,1.5,1.5 main tiles:PP_FUSED_TILE=0:PP_FUSED_TILE=1
 cd "$(dirname "$0")/../.."
 SIZE="512 512 256"; ITERS=60; ROUNDS=2; SPACING=""
 while getopts "s:n:r:p:" o; do

@@ -165,117 +165,5 @@ int main(int argc, char** argv) {
     for (auto& k : keys) unsetenv(k.c_str());
     if (auto reload = reinterpret_cast<void (*)(void)>(dlsym(h, "pp_reload_switches"))) reload();
   }
-  // -DPP_DRIFT builds: 100 MHz wall-clock stamps of every block at the quarter points of its march (the last launch of each
-  // kernel): how far apart are the blocks that share an L2?  Spread = newest - oldest stamp over the blocks of one XCD
-  // (block b -> XCD b % 8), in microseconds and in plane steps of that kernel.
-  if (auto drift_read = reinterpret_cast<int (*)(unsigned long long*, int)>(dlsym(h, "pp_debug_drift_read"))) {
-    std::vector<unsigned long long> buf(2 * 1024 * 4);
-    if (auto xcc_read = reinterpret_cast<int (*)(unsigned*, int)>(dlsym(h, "pp_debug_drift_xcc_read"))) {
-      std::vector<unsigned> xcc(2 * 1024);
-      if (xcc_read(xcc.data(), (int)xcc.size()) > 0) {
-        // HW_REG_XCC_ID (low 4 bits: the XCD) of blocks 0..23 of kernel A, and how many blocks b have XCC_ID & 15 == b % 8
-        int agree = 0, nb = 0;
-        for (int b = 0; b < 1024; ++b) if (buf.size() && xcc[b]) { ++nb; }
-        printf("xcc ids of blocks 0..23 (kernel A, raw register & 0xff):");
-        for (int b = 0; b < 24; ++b) printf(" %u", xcc[b] & 0xffu);
-        for (int b = 0; b < 512; ++b) agree += ((xcc[b] & 15u) == (unsigned)(b % 8));
-        printf("\n  blocks 0..511 with XCC_ID & 15 == b %% 8: %d of 512; distinct ids per residue:", agree);
-        for (int r = 0; r < 8; ++r) { unsigned m = 0; for (int b = r; b < 512; b += 8) m |= 1u << (xcc[b] & 15u); printf(" %d:%#x", r, m); }
-        printf("\n");
-        (void)nb;
-      }
-    }
-    if (drift_read(buf.data(), (int)buf.size()) > 0) {
-      if (const char* dump = getenv("KB_DRIFT_DUMP")) {   // raw stamps: kernel block q0 q1 q2 q3 (10 ns ticks), for offline analysis
-        if (FILE* fh = fopen(dump, "w")) {
-          for (int k = 0; k < 2; ++k)
-            for (int b = 0; b < 1024; ++b) {
-              const unsigned long long* e = &buf[((size_t)k * 1024 + b) * 4];
-              if (e[3]) fprintf(fh, "%d %d %llu %llu %llu %llu\n", k, b, e[0], e[1], e[2], e[3]);
-            }
-          fclose(fh);
-        }
-      }
-      for (int k = 0; k < 2; ++k) {
-        double step_us = 0.0; int nb = 0;
-        for (int b = 0; b < 1024; ++b) {
-          const unsigned long long* e = &buf[((size_t)k * 1024 + b) * 4];
-          if (e[0] && e[3] > e[0]) { step_us += 0.01 * (double)(e[3] - e[0]); ++nb; }
-        }
-        if (!nb) continue;
-        step_us /= nb;   // mean time from the first to the last quarter mark = 3/4 of a march
-        printf("drift kernel %c: %d blocks, first-to-last quarter mark %.1f us\n", k ? 'B' : 'A', nb, step_us);
-        // Do the two blocks that (presumably) share a CU -- XCD-local indices j and j + 32, i.e. blocks b and b + 256 of a
-        // 512-block launch -- finish together?  d = end stamp of b + 256 minus end stamp of b.
-        {
-          double sum = 0.0, sabs = 0.0, lo = 1e30, hi = -1e30; int np = 0;
-          double lo_first = 1e30, hi_first = -1e30, lo_second = 1e30, hi_second = -1e30;
-          for (int b = 0; b < 256; ++b) {
-            const unsigned long long e0 = buf[((size_t)k * 1024 + b) * 4 + 3], e1 = buf[((size_t)k * 1024 + b + 256) * 4 + 3];
-            if (!e0 || !e1) continue;
-            const double dd = 0.01 * ((double)e1 - (double)e0);
-            sum += dd; sabs += dd < 0 ? -dd : dd; if (dd < lo) lo = dd; if (dd > hi) hi = dd; ++np;
-            if ((b & 7) == 0) {   // XCD 0 only: spread inside each half of the run
-              const double t0 = 0.01 * (double)e0, t1 = 0.01 * (double)e1;
-              if (t0 < lo_first) lo_first = t0; if (t0 > hi_first) hi_first = t0;
-              if (t1 < lo_second) lo_second = t1; if (t1 > hi_second) hi_second = t1;
-            }
-          }
-          if (np) printf("  pairs (b, b + 256): end(b + 256) - end(b) mean %.1f us, mean |.| %.1f us, min %.1f, max %.1f over %d pairs; xcd 0: end spread of blocks j < 32 %.1f us, of j >= 32 %.1f us\n",
-                         sum / np, sabs / np, lo, hi, np, hi_first - lo_first, hi_second - lo_second);
-        }
-        for (int x = 0; x < 8; ++x) {
-          printf("  xcd %d:", x);
-          for (int q = 0; q < 4; ++q) {
-            unsigned long long lo = ~0ull, hi = 0;
-            for (int b = x; b < 1024; b += 8) {
-              const unsigned long long v = buf[((size_t)k * 1024 + b) * 4 + q];
-              if (!v) continue;
-              if (v < lo) lo = v;
-              if (v > hi) hi = v;
-            }
-            printf(" q%d spread %.2f us", q, hi >= lo ? 0.01 * (double)(hi - lo) : -1.0);
-          }
-          printf("\n");
-        }
-      }
-    }
-  }
-  // -DPP_TRACE builds: per-wave shader-clock stamps at the plane loop's barriers (one interior block per kernel)
-  if (auto trace_read = reinterpret_cast<int (*)(unsigned*, int)>(dlsym(h, "pp_debug_trace_read"))) {
-    const int STEPS = 140, SLOTS = 6;
-    std::vector<unsigned> buf(2 * 8 * STEPS * SLOTS);
-    if (trace_read(buf.data(), (int)buf.size()) > 0 && getenv("KBENCH_PHASES")) {
-      // small-grid kernels: phase stamps (steps 0..8, slot 0) of the first eight waves, clocks since wave 0's phase 0
-      for (int k = 0; k < 2; ++k) {
-        printf("phases kernel %c (0 entry, 1 halt read, 2 fold done, 8 images in LDS, 3 smoothing input ready, 4 x done, 5 y done, 6 z done, 7 end)\n", k ? 'B' : 'A');
-        // rows 0..3: waves 0..3 of the middle block, rows 4..7: waves 0..3 of the last block; shader clocks / 10 ns ticks
-        const unsigned base = buf[((k * 8 + 0) * STEPS + 0) * SLOTS + 0], wbase = buf[((k * 8 + 0) * STEPS + 0) * SLOTS + 1];
-        for (int w = 0; w < 8; w += 2) {
-          printf("  %s w%d:", w < 4 ? "mid " : "last", w & 3);
-          for (int s : {0, 1, 2, 8, 3, 4, 5, 6, 7})
-            printf(" p%d=%d/%.2fus", s, (int)(buf[((k * 8 + w) * STEPS + s) * SLOTS + 0] - base),
-                   0.01 * (int)(buf[((k * 8 + w) * STEPS + s) * SLOTS + 1] - wbase));
-          printf("\n");
-        }
-      }
-    } else if (trace_read(buf.data(), (int)buf.size()) > 0) {
-      for (int k = 0; k < 2; ++k) {
-        printf("trace kernel %c: step | per wave: t(slot1)-t(slot0) ... (shader clocks since slot 0 of wave 0)\n", k ? 'B' : 'A');
-        for (int s = 20; s < 32; ++s) {
-          const unsigned base = buf[((k * 8 + 0) * STEPS + s) * SLOTS + 0];
-          printf("  step %3d:", s);
-          for (int w = 0; w < 8; ++w) {
-            printf(" w%d[", w);
-            for (int q = 0; q < (k ? 4 : 5); ++q) printf("%s%d", q ? " " : "", (int)(buf[((k * 8 + w) * STEPS + s) * SLOTS + q] - base));
-            printf("]");
-          }
-          printf("\n");
-        }
-        const unsigned t0 = buf[((k * 8 + 0) * STEPS + 20) * SLOTS + 0], t1 = buf[((k * 8 + 0) * STEPS + 120) * SLOTS + 0];
-        printf("  100 steps of wave 0: %u clocks = %.1f per step\n", t1 - t0, (t1 - t0) / 100.0);
-      }
-    }
-  }
   return 0;
 }

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
-"""Instruction histogram of one disassembled kernel (tools/kbench/mini.sh writes /tmp/mini_<kernel>.s).
+"""Instruction histogram of one disassembled kernel (its part of `llvm-objdump -d` of the code object).
 
-    python tools/r5/isa_stats.py /tmp/mini_k_fused2_force_smooth.s [--top 25]
+    python tools/r5/isa_stats.py /tmp/k_fused2_force_smooth.s [--top 25]
 
 Classes: vector ALU (v_*), scalar (s_* except waits / nops / barriers), LDS (ds_*), vector memory (buffer_* / global_*),
 waits.  A v_cndmask whose VCC / SGPR-pair mask was last written by a scalar instruction is counted separately

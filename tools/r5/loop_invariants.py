@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Vector registers a kernel's plane loop reads but never writes (loop-invariant per-thread state), from a disassembly.
-    python tools/r5/loop_invariants.py /tmp/mini_k_fused2_force_smooth.s FIRST_LINE LAST_LINE
+    python tools/r5/loop_invariants.py /tmp/k_fused2_force_smooth.s FIRST_LINE LAST_LINE
 """
 import re
 import sys
