@@ -295,6 +295,47 @@ int pp_label_contour_u8(pp_ctx* ctx, const uint8_t* mask, const int size[3], uin
 int pp_distance_map_f32(pp_ctx* ctx, const uint8_t* mask, const pp_geom* g, int want_signed,
                         int inside_positive, float* out);
 
+/* ---- label comparison -------------------------------------------------------------- */
+/* The three counts every volume metric is made of (label/comparison.py:157-180, :211-213): counts (host, 3 x int64) =
+ * |A|, |B|, |A and B| over n voxels, non-zero = foreground, one streaming pass over both masks.  Synchronises. */
+int pp_overlap_counts_u8(pp_ctx* ctx, const uint8_t* a, const uint8_t* b, size_t n, int64_t counts[3]);
+/* sitk.BinaryContourImageFilter, FullyConnectedOn (label/comparison.py:51-54): object voxels with a background voxel in
+ * their 26-neighbourhood -- the border rule of pp_distance_map_f32; fully_connected = 0 gives the face rule of
+ * pp_label_contour_u8.  Voxels outside the image are not neighbours. */
+int pp_binary_contour_u8(pp_ctx* ctx, const uint8_t* mask, const int size[3], int fully_connected, uint8_t* out);
+/* sitk.LabelContour(label[:, :, i]) for every slice i at once (label/comparison.py:373-374): object voxels with a
+ * background voxel among their four in-plane face neighbours. */
+int pp_slice_contour_u8(pp_ctx* ctx, const uint8_t* mask, const int size[3], uint8_t* out);
+/* min and max of |in| over n voxels into device_range (DEVICE, 2 floats): the range of sitk.Abs(SignedMaurerDistanceMap)
+ * that itk::LabelStatisticsImageFilter's histogram spans (label/comparison.py:99-106).  No read-back, no synchronisation. */
+int pp_abs_range_f32(pp_ctx* ctx, const float* in, size_t n, float* device_range);
+/* sitk.LabelIntensityStatisticsImageFilter over a distance map, fused with the selection of its samples
+ * (label/comparison.py:99-113; :64-65; itk::DirectedHausdorffDistanceImageFilter behind :89-91).  `select` is a label on
+ * the grid g, `dist` a distance map on it, read only where a sample sits:
+ *   PP_SURFACE_CONTOUR_ABS   samples = sitk.LabelContour(select) (face rule, evaluated on the fly), value = |dist|
+ *   PP_SURFACE_LABEL_POS     samples = every voxel of select, value = max(dist, 0)      (directed Hausdorff)
+ *   PP_SURFACE_NONZERO       samples = every non-zero voxel of select, value = dist     (select is a ready contour)
+ * out (DEVICE, 8-byte aligned): count, fp64 sum and sum of squares, min, max, the count of values <= tau and, when
+ * device_range (DEVICE, 2 floats {lo, hi}, e.g. from pp_abs_range_f32) is not NULL, ITK's 128-bin histogram of the values
+ * over [lo, hi]: bin = min(int((v - lo) / (hi - lo) * 128), 127) in fp64.  Sums run in a fixed order and the bins are
+ * integers: a rerun gives the same bits.  No read-back, no synchronisation. */
+enum { PP_SURFACE_CONTOUR_ABS = 0, PP_SURFACE_LABEL_POS = 1, PP_SURFACE_NONZERO = 2 };
+#define PP_SURFACE_BINS 128
+typedef struct pp_surface_stats {
+  int64_t count;
+  int64_t count_le_tau;
+  double sum, sum_sq;
+  float min, max;                  /* FLT_MAX, -FLT_MAX when count == 0 */
+  float range_lo, range_hi;        /* the histogram's range (0, 0 without device_range) */
+  int64_t hist[PP_SURFACE_BINS];
+} pp_surface_stats;
+int pp_surface_stats_f32(pp_ctx* ctx, const uint8_t* select, const float* dist, const pp_geom* g, int mode, double tau,
+                         const float* device_range, pp_surface_stats* out);
+/* Per z slice, the number of voxels with a != 0 and not_b == 0 (not_b may be NULL: the count of a): sitk.MaskNegated +
+ * sum per slice, and the "both slices empty" test (label/comparison.py:367-385).  per_slice: DEVICE, size[2] x int64.
+ * No read-back, no synchronisation. */
+int pp_slice_masked_count_u8(pp_ctx* ctx, const uint8_t* a, const uint8_t* not_b, const int size[3], int64_t* per_slice);
+
 /* ---- linear registration ----------------------------------------------------------- */
 /* One evaluation of the mean-squares metric (itk::MeanSquaresImageToImageMetricv4, selected at
  * registration/linear.py:141-148, evaluated inside registration.Execute at :238) and its gradient

@@ -103,6 +103,13 @@ class StapleResult(C.Structure):    # pp_staple_result
                 ("degenerate", C.c_int), ("reserved", C.c_int)]
 
 
+SURFACE_CONTOUR_ABS, SURFACE_LABEL_POS, SURFACE_NONZERO = 0, 1, 2
+SURFACE_BINS = 128
+# pp_surface_stats as a numpy record (the struct lives in device memory; the host views the bytes it reads back)
+SURFACE_STATS_DTYPE = np.dtype([("count", "<i8"), ("count_le_tau", "<i8"), ("sum", "<f8"), ("sum_sq", "<f8"), ("min", "<f4"),
+                                ("max", "<f4"), ("range_lo", "<f4"), ("range_hi", "<f4"), ("hist", "<i8", (SURFACE_BINS,))])
+
+
 class PlatipyAmdError(RuntimeError):
     pass
 
@@ -155,6 +162,12 @@ _SIGNATURES = {
                                  C.POINTER(StapleResult)]),
     "pp_label_contour_u8": (C.c_int, [_P, _P, C.POINTER(C.c_int), _P]),
     "pp_distance_map_f32": (C.c_int, [_P, _P, C.POINTER(Geom), C.c_int, C.c_int, _P]),
+    "pp_overlap_counts_u8": (C.c_int, [_P, _P, _P, C.c_size_t, C.POINTER(C.c_int64)]),
+    "pp_binary_contour_u8": (C.c_int, [_P, _P, C.POINTER(C.c_int), C.c_int, _P]),
+    "pp_slice_contour_u8": (C.c_int, [_P, _P, C.POINTER(C.c_int), _P]),
+    "pp_abs_range_f32": (C.c_int, [_P, _P, C.c_size_t, _P]),
+    "pp_surface_stats_f32": (C.c_int, [_P, _P, _P, C.POINTER(Geom), C.c_int, C.c_double, _P, _P]),
+    "pp_slice_masked_count_u8": (C.c_int, [_P, _P, _P, C.POINTER(C.c_int), _P]),
     "pp_meansq_affine_f32": (C.c_int, [_P, _P, C.POINTER(C.c_int), _P, C.POINTER(C.c_int), C.POINTER(C.c_double),
                                        C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double),
                                        C.POINTER(C.c_int), C.c_int, _P, _P, C.POINTER(C.c_double)]),
@@ -478,6 +491,35 @@ class Context:
     def distance_map(self, mask, geom, out, signed=False, inside_positive=False):
         self._chk(self.lib.pp_distance_map_f32(self.h, ptr(mask), C.byref(geom), int(bool(signed)), int(bool(inside_positive)),
                                                ptr(out)), "pp_distance_map_f32")
+
+    # -- label comparison ----------------------------------------------------------
+    def overlap_counts(self, a, b, n):
+        """-> (|A|, |B|, |A and B|) of two uint8 masks, non-zero = foreground (synchronises)."""
+        c = (C.c_int64 * 3)()
+        self._chk(self.lib.pp_overlap_counts_u8(self.h, ptr(a), ptr(b), int(n), c), "pp_overlap_counts_u8")
+        return c[0], c[1], c[2]
+
+    def binary_contour(self, mask, size, out, fully_connected=True):
+        self._chk(self.lib.pp_binary_contour_u8(self.h, ptr(mask), _i3(size), int(bool(fully_connected)), ptr(out)),
+                  "pp_binary_contour_u8")
+
+    def slice_contour(self, mask, size, out):
+        self._chk(self.lib.pp_slice_contour_u8(self.h, ptr(mask), _i3(size), ptr(out)), "pp_slice_contour_u8")
+
+    def abs_range(self, src, n, device_range):
+        """min / max of |src| into `device_range` (2 floats in device memory); nothing is read back."""
+        self._chk(self.lib.pp_abs_range_f32(self.h, ptr(src), int(n), ptr(device_range)), "pp_abs_range_f32")
+
+    def surface_stats(self, select, dist, geom, mode, out, tau=0.0, device_range=None):
+        """pp_surface_stats_f32 into `out`: SURFACE_STATS_DTYPE.itemsize bytes of device memory, 8-byte aligned (an address or
+        a buffer); nothing is read back."""
+        self._chk(self.lib.pp_surface_stats_f32(self.h, ptr(select), ptr(dist), C.byref(geom), int(mode), float(tau),
+                                                ptr(device_range), ptr(out)), "pp_surface_stats_f32")
+
+    def slice_masked_count(self, a, not_b, size, per_slice):
+        """per_slice[z] (int64, device memory) = voxels of slice z with a != 0 and not_b == 0 (not_b None: with a != 0)."""
+        self._chk(self.lib.pp_slice_masked_count_u8(self.h, ptr(a), ptr(not_b), _i3(size), ptr(per_slice)),
+                  "pp_slice_masked_count_u8")
 
     def meansq_affine(self, fixed, fsize, moving, msize, Af, bf, Am, bm, vsize, stride, fixed_mask=None, moving_mask=None):
         """-> (sum sq diff, count, dAm[9], dbm[3]) as a list of 14 floats."""

@@ -202,3 +202,6 @@ int pp_distance_map_f32(pp_ctx* ctx, const uint8_t* mask, const pp_geom* g, int 
 }
 
 }  // extern "C"
+
+// label comparison metrics (overlap counts, contours, the fused surface statistics pass, slice counts)
+#include "pp_compare.h"
