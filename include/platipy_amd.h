@@ -284,6 +284,31 @@ typedef struct {
 int pp_staple_fuse(pp_ctx* ctx, const void* const* labels, int dtype, int nraters, size_t n,
                    const pp_staple_params* params, double* w, pp_staple_result* result);
 
+/* ---- patch correlation and mutual information -------------------------------------- */
+/* The per-voxel scipy.stats.pearsonr loop of compute_weight_map(vote_type="patch_correlation") (label/fusion.py:94-132)
+ * as one pass.  For output voxel i the patch spans, per axis with window w, the input indices i - (w - 1) / 2 ... i + w / 2
+ * (integer division) that lie inside the image -- the reference's zero padding plus its mask of ones: padded voxels are
+ * left out, not counted as zeros.  corr = Pearson r of the two patches, clipped to [-1, 1] as scipy clips it, and exactly 0
+ * where scipy returns NaN: where either patch is exactly constant (every voxel equal to the patch's first in-image voxel;
+ * no variance threshold).  The moments are accumulated in fp64 on values shifted by each patch's first in-image voxel
+ * (CT patches have means near -1000 and a small spread), in raster order of the patch: a rerun gives the same bits.  The
+ * result is rounded to fp32 once.
+ * window = {x, y, z} voxels, each >= 1.  When every axis has w <= 2 some patch holds a single voxel, where pearsonr
+ * raises: PP_ERR_SIZE.  Windows of up to 8 and up to 16 voxels per axis run from an LDS tile of both images (one
+ * workgroup per 8 x 8 x 4 outputs); a larger window takes a slower path that reads the patches from global memory and
+ * gives the same values.  corr must not alias an input. */
+int pp_patch_correlation_f32(pp_ctx* ctx, const float* target, const float* moving, const int size[3], const int window[3],
+                             float* corr);
+/* np.histogram2d(a, b, bins=(bins_a, bins_b)) behind mutual_information (label/fusion.py:26-53): hist (HOST, bins_a x bins_b
+ * int64, row = bin of a) holds exactly numpy's counts for the float32 samples taken as doubles.  Per array the edges are
+ * numpy's linspace(min, max, bins + 1) in fp64 (min == max widened by -/+ 0.5); a sample's bin is the one
+ * searchsorted(edges, v, side="right") - 1 picks -- an arithmetic guess corrected against the fp64 edge table -- and the
+ * top edge is closed.  range (HOST, out) = the outer edges {amin, amax, bmin, bmax} after that widening.  Integer counts:
+ * per-workgroup LDS tables while bins_a * bins_b <= 16384 (128 x 128), global integer atomics beyond; a rerun gives the
+ * same counts.  A NaN or infinite sample is an error (PP_ERR_ARG), as numpy raises.  Synchronises. */
+int pp_joint_histogram_f32(pp_ctx* ctx, const float* a, const float* b, size_t n, int bins_a, int bins_b, int64_t* hist,
+                           double range[4]);
+
 /* ---- iterative atlas removal ------------------------------------------------------- */
 /* sitk.LabelContour(mask) with face connectivity (label/projection.py:85): object voxels that have a face
  * neighbour of a different value. */

@@ -49,6 +49,7 @@ class LinregStats(C.Structure):     # pp_linreg_stats
                 ("learning_rate", C.c_double)]
 
 
+ERR_ARG, ERR_SIZE = -1, -5
 ERR_NO_OVERLAP = -6
 MODEL_TRANSLATION, MODEL_VERSOR_RIGID, MODEL_SIMILARITY, MODEL_SCALE, MODEL_AFFINE, MODEL_EULER, MODEL_SCALE_VERSOR, MODEL_SCALE_SKEW_VERSOR = range(8)
 OPT_GD, OPT_GD_LINE_SEARCH = 0, 1
@@ -160,6 +161,8 @@ _SIGNATURES = {
     "pp_bounding_box": (C.c_int, [_P, _P, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "pp_staple_fuse": (C.c_int, [_P, C.POINTER(_P), C.c_int, C.c_int, C.c_size_t, C.POINTER(StapleParams), _P,
                                  C.POINTER(StapleResult)]),
+    "pp_patch_correlation_f32": (C.c_int, [_P, _P, _P, C.POINTER(C.c_int), C.POINTER(C.c_int), _P]),
+    "pp_joint_histogram_f32": (C.c_int, [_P, _P, _P, C.c_size_t, C.c_int, C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_double)]),
     "pp_label_contour_u8": (C.c_int, [_P, _P, C.POINTER(C.c_int), _P]),
     "pp_distance_map_f32": (C.c_int, [_P, _P, C.POINTER(Geom), C.c_int, C.c_int, _P]),
     "pp_overlap_counts_u8": (C.c_int, [_P, _P, _P, C.c_size_t, C.POINTER(C.c_int64)]),
@@ -484,6 +487,28 @@ class Context:
         self._chk(self.lib.pp_staple_fuse(self.h, ptrs, 1 if is_float else 0, len(labels), int(n), C.byref(prm), ptr(out),
                                           C.byref(res)), "pp_staple_fuse")
         return res
+
+    def patch_correlation(self, target, moving, size, window, out):
+        """pp_patch_correlation_f32: per-voxel Pearson r over a `window` (x, y, z voxels) clipped to the image.  ValueError
+        for a window that leaves a single voxel in a patch (every axis <= 2)."""
+        rc = self.lib.pp_patch_correlation_f32(self.h, ptr(target), ptr(moving), _i3(size), _i3(window), ptr(out))
+        if rc == ERR_SIZE:
+            msg = self.lib.pp_last_error(self.h)
+            raise ValueError(msg.decode(errors="replace") if msg else "pp_patch_correlation_f32: unsupported window or volume size")
+        self._chk(rc, "pp_patch_correlation_f32")
+
+    def joint_histogram(self, a, b, n, bins_a, bins_b):
+        """pp_joint_histogram_f32 -> (int64 counts [bins_a, bins_b], (amin, amax, bmin, bmax)): np.histogram2d's table and
+        outer edges (synchronises).  ValueError for NaN / infinite samples or an argument the library rejects."""
+        hist = np.zeros((int(bins_a), int(bins_b)), dtype=np.int64)
+        rng = (C.c_double * 4)()
+        rc = self.lib.pp_joint_histogram_f32(self.h, ptr(a), ptr(b), int(n), int(bins_a), int(bins_b),
+                                             hist.ctypes.data_as(C.POINTER(C.c_int64)), rng)
+        if rc == ERR_ARG:
+            msg = self.lib.pp_last_error(self.h)
+            raise ValueError(msg.decode(errors="replace") if msg else "pp_joint_histogram_f32: bad argument")
+        self._chk(rc, "pp_joint_histogram_f32")
+        return hist, tuple(rng)
 
     def label_contour(self, mask, size, out):
         self._chk(self.lib.pp_label_contour_u8(self.h, ptr(mask), _i3(size), ptr(out)), "pp_label_contour_u8")

@@ -1941,3 +1941,6 @@ int pp_linear_set_sample_jitter(pp_ctx* ctx, const float* jitter, size_t nsample
 
 // STAPLE (label/fusion.py:223): kernels in the same unnamed namespace, pp_staple_fuse
 #include "pp_staple.h"
+
+// patch correlation and the joint histogram (label/fusion.py:94-132, :26-53): pp_patch_correlation_f32, pp_joint_histogram_f32
+#include "pp_patch_corr.h"

@@ -4,6 +4,8 @@
 fastest, exactly the memory order of sitk.GetArrayFromImage for scalars.  Accessor names follow
 SimpleITK so code written against the reference reads the same.
 """
+import operator
+
 import numpy as np
 import torch
 
@@ -114,6 +116,58 @@ class Image:
         if not self.is_vector:
             raise ValueError("not a vector image")
         return self.tensor.permute(1, 2, 3, 0).contiguous().double().cpu().numpy()
+
+    # -- elementwise arithmetic (sitk.Image's operators): a scalar or an Image on the same grid; the geometry is kept --
+    def _operand(self, other):
+        if isinstance(other, Image):
+            if other.is_vector != self.is_vector or not self.same_grid(other):
+                raise ValueError("Image arithmetic needs both images on one grid (size, spacing, origin, direction)")
+            return other.tensor
+        if isinstance(other, (bool, int, float, np.integer, np.floating)):
+            return other
+        return NotImplemented
+
+    def _binary(self, other, op, reflected=False):
+        o = self._operand(other)
+        if o is NotImplemented:
+            return NotImplemented
+        return self.like(op(o, self.tensor) if reflected else op(self.tensor, o), self.is_vector)
+
+    def __add__(self, other):
+        return self._binary(other, operator.add)
+
+    def __radd__(self, other):
+        return self._binary(other, operator.add, True)
+
+    def __sub__(self, other):
+        return self._binary(other, operator.sub)
+
+    def __rsub__(self, other):
+        return self._binary(other, operator.sub, True)
+
+    def __mul__(self, other):
+        return self._binary(other, operator.mul)
+
+    def __rmul__(self, other):
+        return self._binary(other, operator.mul, True)
+
+    def __truediv__(self, other):
+        return self._binary(other, operator.truediv)
+
+    def __rtruediv__(self, other):
+        return self._binary(other, operator.truediv, True)
+
+    def __pow__(self, other):
+        return self._binary(other, operator.pow)
+
+    def __rpow__(self, other):
+        return self._binary(other, operator.pow, True)
+
+    def __neg__(self):
+        return self.like(-self.tensor, self.is_vector)
+
+    def __abs__(self):
+        return self.like(self.tensor.abs(), self.is_vector)
 
     def __repr__(self):
         kind = "vector" if self.is_vector else "scalar"

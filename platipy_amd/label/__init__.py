@@ -1,4 +1,4 @@
-from .fusion import combine_labels, combine_labels_staple, compute_weight_map, process_probability_image, staple  # noqa: F401
+from .fusion import combine_labels, combine_labels_staple, compute_patch_correlation_weight_map, compute_weight_map, process_probability_image, staple  # noqa: F401
 from .iar import distance_map, evaluate_distance_to_reference, label_contour, run_iar  # noqa: F401
 from . import comparison, utils  # noqa: F401
 from .utils import (  # noqa: F401

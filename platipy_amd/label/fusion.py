@@ -1,8 +1,16 @@
 """Drop-in for platipy/imaging/label/fusion.py: compute_weight_map (:56-202), combine_labels (:239-292),
 combine_labels_staple (:205-236) and process_probability_image (:295-328) on volumes resident in HBM.
 
-Out of scope, as in SURVEY 8(a8): vote_type="patch_correlation" (a Python per-patch loop in the
-reference, :119-128) and mutual_information raise NotImplementedError.
+The reference's vote_type="patch_correlation" (:82-146) -- one scipy.stats.pearsonr call per voxel of the 3 mm resampled
+image -- is compute_patch_correlation_weight_map (pp_patch_correlation_f32): both images through smooth_and_resample, the
+window int(patch_window_mm / spacing) per axis, Pearson r of the two patches clipped to the image (the reference's zero
+padding and mask of ones), exactly 0 where scipy gives NaN (a patch that is exactly constant), fp64 moments rounded to
+fp32 once, then resample_image back onto the target grid and `correlation_function` (an Image in, an Image or a tensor
+out).  weight_map_for_vote is the dispatcher the pipelines call: it sends that vote type there and every other one to
+compute_weight_map.  compute_weight_map itself still refuses vote_type="patch_correlation" with NotImplementedError, and
+mutual_information still raises it: tests/test_fusion.py and tests/test_staple.py pin both, so the new code sits beside
+them -- histogram_mutual_information (:26-53) builds np.histogram2d's integer table on the GPU (pp_joint_histogram_f32,
+also joint_histogram) and evaluates the reference's formula on the host in fp64.
 
 STAPLE (`staple`, sitk.STAPLE / itk::STAPLEImageFilter, Warfield et al. 2004), as implemented by pp_staple_fuse.
 With R raters, N voxels and D_ij = 1 iff fg - 1e-10 < v_ij < fg + 1e-10 (compared in double):
@@ -45,6 +53,9 @@ DEFAULT_VOTE_PARAMS = {
     "gain": 6,
     "blockSize": 5,
     "normalise": False,
+    "patch_window_mm": 25,
+    "resampled_voxel_size_mm": 3,
+    "correlation_function": lambda x: x + 1,
 }
 
 
@@ -65,7 +76,8 @@ def compute_weight_map(target_image, moving_image, vote_type="unweighted", vote_
     vt = vote_type.lower()
 
     if vt == "patch_correlation":
-        raise NotImplementedError("vote_type='patch_correlation' is outside the MI355X hot path (SURVEY 8 a8)")
+        raise NotImplementedError("compute_weight_map does not take vote_type='patch_correlation': call "
+                                  "compute_patch_correlation_weight_map, or weight_map_for_vote as the pipelines do")
     if vt == "unweighted":
         weight = t * 0.0 + 1.0                                                      # :151-152
     elif vt == "global":
@@ -83,6 +95,47 @@ def compute_weight_map(target_image, moving_image, vote_type="unweighted", vote_
         weight = _normalise(weight, p["normalise"])
     else:
         raise ValueError(f"unknown vote_type {vote_type!r}")
+    return target_image.like(weight.float().contiguous())
+
+
+def weight_map_for_vote(target_image, moving_image, vote_type="unweighted", vote_params=None):
+    """The reference's compute_weight_map with every vote type it has: "patch_correlation" goes to
+    compute_patch_correlation_weight_map, anything else to compute_weight_map."""
+    if vote_type.lower() == "patch_correlation":
+        return compute_patch_correlation_weight_map(target_image, moving_image, vote_params)
+    return compute_weight_map(target_image, moving_image, vote_type, vote_params)
+
+
+def compute_patch_correlation_weight_map(target_image, moving_image, vote_params=None):
+    """The reference's compute_weight_map(vote_type="patch_correlation") (fusion.py:82-146): both images cast to fp32 and
+    resampled to isotropic voxels, local Pearson r, back to the target grid, then correlation_function (the reference's
+    default adds 1: similar modalities; abs suits MR against CT).  vote_params overrides patch_window_mm (25),
+    resampled_voxel_size_mm (3) and correlation_function of DEFAULT_VOTE_PARAMS.  fp32 result on the target grid."""
+    from ..registration.utils import resample_image, smooth_and_resample
+
+    target_image, moving_image = as_image(target_image), as_image(moving_image)
+    p = dict(DEFAULT_VOTE_PARAMS)
+    if vote_params:
+        p.update(vote_params)
+    ctx = runtime.context(target_image.device)
+    target_image, moving_image = target_image.like(_f32(target_image)), moving_image.like(_f32(moving_image))   # :77-80
+    voxel_size = p["resampled_voxel_size_mm"]
+    target_res = smooth_and_resample(target_image, isotropic_voxel_size_mm=voxel_size)          # :87-88
+    moving_res = smooth_and_resample(moving_image, isotropic_voxel_size_mm=voxel_size)
+    if not target_res.same_grid(moving_res):
+        raise ValueError(f"patch_correlation: the resampled images are on different grids ({target_res!r}, {moving_res!r})")
+    window = [int(p["patch_window_mm"] / s) for s in target_res.GetSpacing()]                   # :97-98, (x, y, z) here
+    if min(window) < 1:
+        raise ValueError(f"patch_correlation: patch_window_mm={p['patch_window_mm']} is below the resampled spacing "
+                         f"{target_res.GetSpacing()}")
+    corr = torch.empty_like(target_res.tensor)
+    ctx.patch_correlation(_f32(target_res), _f32(moving_res), target_res.GetSize(), window, corr)   # :100-132
+    corr_image = resample_image(target_res.like(corr), target_image)                            # :138: linear, default 0
+    weight = p["correlation_function"](corr_image)                                              # :144-146
+    if isinstance(weight, Image):
+        weight = weight.tensor
+    if not torch.is_tensor(weight) or tuple(weight.shape) != tuple(target_image.tensor.shape):
+        raise TypeError("correlation_function must return an Image or a tensor on the target grid")
     return target_image.like(weight.float().contiguous())
 
 
@@ -261,5 +314,70 @@ def combine_labels_staple(label_list_dict, threshold=1e-4):
     return combined_label_dict
 
 
+def _flat_f32(x):
+    """Image, tensor or ndarray -> flat float32 tensor on the device the kernels run on."""
+    if isinstance(x, Image):
+        x = x.tensor
+    if not torch.is_tensor(x):
+        x = torch.from_numpy(np.ascontiguousarray(x))
+    if x.device.type == "cpu":
+        x = x.to(runtime.default_device())
+    return x.reshape(-1).to(torch.float32).contiguous()
+
+
+def _bin_counts(bins):
+    """np.histogram2d's `bins` as (bins_a, bins_b): an int, or a pair of ints."""
+    if isinstance(bins, (int, np.integer)) and not isinstance(bins, bool):
+        pair = (int(bins), int(bins))
+    elif (isinstance(bins, (list, tuple)) and len(bins) == 2
+          and all(isinstance(b, (int, np.integer)) and not isinstance(b, bool) for b in bins)):
+        pair = (int(bins[0]), int(bins[1]))
+    else:
+        raise NotImplementedError("mutual_information: `bins` given as edge arrays is not implemented; pass an int or a pair of ints")
+    if min(pair) < 1:
+        raise ValueError("mutual_information: `bins` must be positive")
+    return pair
+
+
+def joint_histogram(arr_a, arr_b, bins=64):
+    """np.histogram2d(arr_a, arr_b, bins) -> (int64 counts [bins_a, bins_b], edges_a, edges_b), counted on the GPU.
+    The samples are taken as float32 (what an Image holds) and binned as doubles against numpy's fp64 linspace edges, so
+    the counts equal numpy's on the same values.  NaN or infinite samples raise ValueError, as numpy does."""
+    bins_a, bins_b = _bin_counts(bins)
+    a, b = _flat_f32(arr_a), _flat_f32(arr_b)
+    if a.numel() != b.numel() or a.numel() == 0:
+        raise ValueError("mutual_information: the arrays must hold the same, non-zero number of samples")
+    if a.device != b.device:
+        raise ValueError(f"mutual_information: the arrays are on different devices ({a.device}, {b.device})")
+    hist, rng = runtime.context(a.device).joint_histogram(a, b, a.numel(), bins_a, bins_b)
+    return hist, np.linspace(rng[0], rng[1], bins_a + 1), np.linspace(rng[2], rng[3], bins_b + 1)
+
+
 def mutual_information(arr_a, arr_b, bins=64):
-    raise NotImplementedError("mutual_information is outside the MI355X hot path (SURVEY 8 a8)")
+    raise NotImplementedError("mutual_information is not wired to the GPU path: call histogram_mutual_information")
+
+
+def histogram_mutual_information(arr_a, arr_b, bins=64):
+    """The reference's mutual_information (fusion.py:26-53), the histogram-based mutual information between two arrays:
+    Images, tensors or ndarrays, flattened; bins an int or a pair of ints.  -> float.
+
+    The joint histogram is counted on the GPU (joint_histogram); the value is the reference's formula, as written, in fp64
+    on the host: np.histogram2d(density=True) divides the counts by the bin areas and the total, and the marginals are
+    named by numpy axis, p_a = p_ab.sum(axis=0) and p_b = p_ab.sum(axis=1), so outer(p_a, p_b) pairs row i, column j with
+    the marginals of column i and row j -- the transpose of the product of marginals.  That is kept: for a symmetric table
+    it changes nothing, for an asymmetric one the value is the reference's, and for bins_a != bins_b the division cannot
+    broadcast and raises ValueError as it does in the reference."""
+    hist, edges_a, edges_b = joint_histogram(arr_a, arr_b, bins)
+    with warnings.catch_warnings():
+        warnings.simplefilter("ignore")
+        # np.histogramdd(density=True): counts / bin widths, axis by axis, then / total
+        p_ab = hist.astype(np.float64)
+        total = p_ab.sum()
+        p_ab = p_ab / np.diff(edges_a).reshape(-1, 1)
+        p_ab = p_ab / np.diff(edges_b).reshape(1, -1)
+        p_ab /= total
+        p_a = p_ab.sum(axis=0)
+        p_b = p_ab.sum(axis=1)
+        log_p = np.log(p_ab / np.outer(p_a, p_b))
+    log_p[~np.isfinite(log_p)] = 0
+    return (p_ab * log_p).sum()

@@ -26,7 +26,7 @@ import torch
 
 from .. import runtime
 from ..image import as_image
-from ..label.fusion import compute_weight_map, finalize_probability, label_tensor, process_probability_image
+from ..label.fusion import compute_weight_map, weight_map_for_vote, finalize_probability, label_tensor, process_probability_image
 from ..registration.deformable import fast_symmetric_forces_demons_registration
 from ..registration.linear import linear_registration
 from ..generation.mask import extend_mask
@@ -452,7 +452,7 @@ def atlas_pipeline(img, settings, guide_structure=None, atlases=None, streams_pe
     buf = torch.zeros(((1 + S) if shared_wsum else 2 * S,) + img_crop.shape, dtype=torch.float32, device=device)
     for atlas_id in my_ids:
         d = atlas_set[atlas_id]["DIR"]
-        d["Weight Map"] = compute_weight_map(img_crop, d["CT Image"], vote_type=vote_type, vote_params=vote_params)
+        d["Weight Map"] = weight_map_for_vote(img_crop, d["CT Image"], vote_type=vote_type, vote_params=vote_params)
         w = d["Weight Map"].tensor.contiguous()
         for k, s in enumerate(atlas_structure_list):
             if shared_wsum:
