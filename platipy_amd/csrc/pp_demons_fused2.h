@@ -857,6 +857,18 @@ struct fused2_force_lds {
   static constexpr int SZ_U = G::SZ_U;
   static constexpr int SZ_XT = 3 * G::UH * fused2_xtile<SH>::XP;     // x-pass tile (>= G::SZ_X: the row pitch may be padded)
 };
+// STRIPS: the MASK instances up to radius 2 fetch the image pair as 16-byte strips over the WHOLE image tile (strip_geom<R, SH, 1>:
+// rows ty0 - R - 1 .. ty0 + TY + R, the x halo padded to whole strips) straight into the packed tile -- one 16-byte load per
+// array and two 16-byte LDS stores per thread and plane instead of 2 KU + 2 four-byte loads, KU + 1 eight-byte stores and the
+// sentinel select per owned voxel; the border ring is part of the strips.  The packed tile is double-buffered: the plane after
+// the window centre is published while the centre is still being read, and an owner takes its own voxel of that plane from
+// there (one more ds_read_b64 per voxel) instead of from a load of its own, so the register window is two planes (below, centre)
+// and nothing of a plane is fetched twice.  Two tiles + s_u + s_x: 69 KB at radius 2 with 64 x 16 tiles, 75 KB for the mixed
+// launch -- two blocks per CU; at radius 3 the mixed launch would need 83 KB, so radius 3 keeps the per-voxel fetch.
+template <int R, bool MASK>
+struct fused2_force_strips {
+  static constexpr bool value = MASK && R <= 2;
+};
 // The kernel's body for ONE tile shape; the three LDS objects come from the __global__ wrapper below (as for kernel B).
 template <int R, int SH, bool UNROLL, bool SUM, bool NT, bool MASK, bool BIG = false>   // (BIG: as in fused2_warp_body)
 __device__ __forceinline__ void fused2_force_body(const float* __restrict__ F, const float* __restrict__ Mw, const float* __restrict__ D,
@@ -868,6 +880,11 @@ __device__ __forceinline__ void fused2_force_body(const float* __restrict__ F, c
   constexpr int NTH = G::NTH, TX = G::TX, TY = G::TY, W = 2 * R + 1;
   constexpr int NXI = (3 * G::XI + NTH - 1) / NTH;
   constexpr bool SOFF_F = !BIG;   // (as in fused2_warp_body)
+  constexpr bool STRIPS = fused2_force_strips<R, MASK>::value;
+  using SG = strip_geom<R, SH, 1>;
+  constexpr int TILE2 = fused2_force_lds<R, SH>::SZ_IMG2 / 2;   // one packed tile (float2); STRIPS: s_mf holds two
+  static_assert(!STRIPS || (SG::NSL == 1 && SG::TH == G::MH && SG::UW <= G::MWP && G::MWP % 2 == 0 && SG::RP >= R + 1),
+                "one strip per thread; strips cover the image tile and stay 16-byte aligned at the packed tile's pitch");
   static_assert(!(BIG && MASK), "the MASK instances keep whole arrays under 2^31 bytes");
   float* const smem = s_u;   // (the reduction scratch of the prologue: 3 * 8 doubles)
   if (st->halt) return;   // (written by an earlier launch)
@@ -941,8 +958,9 @@ __device__ __forceinline__ void fused2_force_body(const float* __restrict__ F, c
     const unsigned wslot = (unsigned)((uy + 1) * G::MWP + (ux + 1));
     // (read slot stored one tile row UP: the four neighbour reads of the ESM pass are then non-negative constant offsets from
     // one address register -- DS instructions take no negative immediate, and l - 1 / l - MWP each held a register per round)
-    const unsigned rslot = (unsigned)((yc - (ty0 - R - 1) - 1) * G::MWP + (xc - (tx0 - R - 1)));
-    slots[k] = rslot | (wslot << 16);
+    // (STRIPS: the tile's columns start at tx0 - RP, a strip boundary)
+    const unsigned rslot = (unsigned)((yc - (ty0 - R - 1) - 1) * G::MWP + (xc - (tx0 - (STRIPS ? SG::RP : R + 1))));
+    slots[k] = STRIPS ? rslot : rslot | (wslot << 16);
     unsigned fl = 0;
     if (e < G::NU) fl |= F_VALID;
     if (e < G::NU && xg >= tx0 && xg < tx0 + TX && xg < d.nx && yg >= ty0 && yg < ty0 + TY && yg < d.ny) fl |= F_CNT;
@@ -957,7 +975,7 @@ __device__ __forceinline__ void fused2_force_body(const float* __restrict__ F, c
   int brd_w = -1;
   unsigned brd_g = 0;
   float brd_oov = -FLT_MAX;
-  if (t < G::NB) {
+  if (!STRIPS && t < G::NB) {
     int my, mx;
     if (t < G::MW) { my = 0; mx = t; }
     else if (t < 2 * G::MW) { my = G::MH - 1; mx = t - G::MW; }
@@ -967,6 +985,22 @@ __device__ __forceinline__ void fused2_force_body(const float* __restrict__ F, c
     brd_w = my * G::MWP + mx;
     brd_g = ((unsigned)yc * sy + (unsigned)xc) * 4u;
   }
+  // STRIPS: this thread's strip of the image tile (packed-tile slot in float2 units; lanes without one load strip 0 and store
+  // nothing).  smap: the element map of pp_strip_setup, and from bit 8 one bit per position that lies outside the volume
+  // (its warped half publishes the sentinel); 0xE4 = a strip inside the volume, stored as loaded.
+  pp_strip sst{0u, -1, 0xE4u};
+  unsigned smap = 0xE4u;
+  if constexpr (STRIPS) {
+    sst = pp_strip_setup(t, SG::NS, SG::SPR, G::MWP, tx0 - SG::RP, ty0 - R - 1, d, a.px);
+    const int ss = t < SG::NS ? t : 0;
+    const int uy = ss / SG::SPR, xs0 = tx0 - SG::RP + 4 * (ss - uy * SG::SPR), yg = ty0 - R - 1 + uy;
+    const bool yout = yg < 0 || yg >= d.ny;
+    smap = sst.jm;
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+      if (yout || xs0 + i < 0 || xs0 + i >= d.nx) smap |= 0x100u << i;
+  }
+  int cb = 0;   // STRIPS: the tile (0 / 1) that holds the window centre
   int xsrc[NXI], xdst[NXI];
   fused2_xpass_setup<R, SH, NXI>(t, xsrc, xdst);
   const int yb = cy * fused2_xtile<SH>::XP + 2 * cx;
@@ -987,6 +1021,29 @@ __device__ __forceinline__ void fused2_force_body(const float* __restrict__ F, c
   float bm_n = 0.0f, bf_n = 0.0f;
   float a_ssd = 0.0f, a_ssc = 0.0f, a_n = 0.0f;   // <= ~40 terms per thread: fp32 is exact enough, folded in fp64 below
 
+  float4 sm4 = make_float4(0.0f, 0.0f, 0.0f, 0.0f), sf4 = sm4;   // STRIPS: the strip in flight (warped, fixed)
+  auto load_strips = [&](int zc) {   // (every lane, see kernel B's load_plane)
+    const size_t po = (size_t)zc * sz;
+    sm4 = pp_gld4(reinterpret_cast<const char*>(Mw + po), sst.goff);
+    sf4 = pp_gld4(reinterpret_cast<const char*>(F + po), sst.goff);
+  };
+  auto write_strips = [&](int buf) {   // the strip in flight -> packed tile `buf`, (warped, fixed) interleaved
+    if (sst.slot >= 0) {
+      float m[4] = {sm4.x, sm4.y, sm4.z, sm4.w}, f[4] = {sf4.x, sf4.y, sf4.z, sf4.w};
+      if (smap != 0xE4u) {   // tiles on the volume's x / y border only: clamped voxels (ZeroFluxNeumann), sentinels outside
+        const unsigned j = pp_opaque(smap);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+          const unsigned e = (j >> (2 * i)) & 3u;
+          m[i] = ((j >> (8 + i)) & 1u) ? FLT_MAX : pp_pick4(sm4.x, sm4.y, sm4.z, sm4.w, e);
+          f[i] = pp_pick4(sf4.x, sf4.y, sf4.z, sf4.w, e);
+        }
+      }
+      float4* const p = reinterpret_cast<float4*>(s_mf + buf * TILE2 + sst.slot);
+      p[0] = make_float4(m[0], f[0], m[1], f[1]);
+      p[1] = make_float4(m[2], f[2], m[3], f[3]);
+    }
+  };
   auto publish = [&]() {   // window centre (mcur, fcur) + border ring -> packed image tile
 #pragma unroll
     for (int k = 0; k < G::KU; ++k)
@@ -1025,8 +1082,13 @@ __device__ __forceinline__ void fused2_force_body(const float* __restrict__ F, c
       const bool full_round = (k + 1) * NTH <= G::NU;
       const bool valid = full_round || (fl & F_VALID);
       if (full_round || __any(valid)) {
-        const pp_v2f* const lp2 = reinterpret_cast<const pp_v2f*>(s_mf) + (slots[k] & 0xffffu);   // (the slot one row up, see the setup)
+        const pp_v2f* const lp2 = reinterpret_cast<const pp_v2f*>(s_mf + (STRIPS ? cb * TILE2 : 0)) + (slots[k] & 0xffffu);   // (the slot one row up, see the setup)
         const pp_v2f xm2 = lp2[G::MWP - 1], xp2 = lp2[G::MWP + 1], ym2 = lp2[0], yp2 = lp2[2 * G::MWP];
+        if constexpr (STRIPS) {   // the owned voxel one plane up, from the tile that was published last
+          const pp_v2f up2 = (reinterpret_cast<const pp_v2f*>(s_mf + (cb ^ 1) * TILE2) + (slots[k] & 0xffffu))[G::MWP];
+          wnext[k][0] = up2[0];
+          wnext[k][1] = up2[1];
+        }
         const float2 xm = make_float2(xm2[0], xm2[1]), xp = make_float2(xp2[0], xp2[1]), ym = make_float2(ym2[0], ym2[1]), yp = make_float2(yp2[0], yp2[1]);
         const unsigned flb = pp_opaque(fl);   // (predicates formed here: hoisted, they would hold six scalar registers per voxel)
         const float mmax = fmaxf(fmaxf(fmaxf(xm.x, xp.x), fmaxf(ym.x, yp.x)), fmaxf(fmaxf(wprev[k][0], wnext[k][0]), wcur[k][0]));
@@ -1082,6 +1144,14 @@ __device__ __forceinline__ void fused2_force_body(const float* __restrict__ F, c
       }
     }
     }
+    if constexpr (STRIPS) {   // (the plane above comes from the other tile on the next pass, which then holds the centre)
+#pragma unroll
+      for (int k = 0; k < G::KU; ++k) {
+        wprev[k][0] = wcur[k][0]; wcur[k][0] = wnext[k][0];
+        wprev[k][1] = wcur[k][1]; wcur[k][1] = wnext[k][1];
+      }
+      cb ^= 1;
+    } else {
 #pragma unroll
     for (int k = 0; k < G::KU; ++k) {
       wprev[k][0] = wcur[k][0]; wcur[k][0] = wnext[k][0]; wnext[k][0] = win_[k][0];
@@ -1089,6 +1159,7 @@ __device__ __forceinline__ void fused2_force_body(const float* __restrict__ F, c
     }
     bm = bm_n;
     bf = bf_n;
+    }
   };
 
   float rg[3][2][W];
@@ -1142,6 +1213,15 @@ __device__ __forceinline__ void fused2_force_body(const float* __restrict__ F, c
       wcur[k][0] = pp_bld(rmc, own_g[k]);  wcur[k][1] = pp_bld(rfc, own_g[k]);
       wnext[k][0] = pp_bld(rmn, own_g[k]); wnext[k][1] = pp_bld(rfn, own_g[k]);
     }
+    if constexpr (STRIPS) {   // both tiles (centre, plane above), the strip after them in flight
+      load_strips(zc0);
+      write_strips(0);
+      load_strips(pp_clampi(zc0 + 1, 0, d.nz - 1));
+      write_strips(1);
+      load_strips(pp_clampi(zc0 + 2, 0, d.nz - 1));
+      __syncthreads();
+      esm(zc0);
+    } else {
     if (brd_w >= 0) {
       bm = pp_bld(rmc, brd_g);
       bf = pp_bld(rfc, brd_g);
@@ -1153,6 +1233,7 @@ __device__ __forceinline__ void fused2_force_body(const float* __restrict__ F, c
     {   // step 0's image loads (see the end of the plane step)
       const int n1 = pp_clampi(zs + 1, 0, d.nz - 1);
       if (nsteps > 1 && n1 != zc0) prefetch(n1);
+    }
     }
     if constexpr (SUM) load_dsum(zs - R);
     __syncthreads();
@@ -1169,7 +1250,18 @@ __device__ __forceinline__ void fused2_force_body(const float* __restrict__ F, c
     const bool emit = (zo >= z0) && (zo <= zo_last) && out_ok;
     if constexpr (MASK) pp_pairprio_peek(yprio);
     // ---- interval 1: x pass of plane `cur` (s_u -> s_x) | publish the image tile of plane `nxt` ----
-    if (fresh_next) publish();
+    if constexpr (STRIPS) {
+      // The strip in flight holds plane nxt + 1: it goes to the tile the last ESM pass had as its centre, and the strip of
+      // plane nxt + 2 is requested right behind it -- a whole plane step before it is stored, and ahead of this step's field
+      // stores and D loads, so that no wait for those has it pending (vmcnt retires in issue order).  Steps that publish
+      // nothing re-read the plane the next publishing step needs.
+      if (fresh_next) write_strips(cb ^ 1);
+      __builtin_amdgcn_sched_barrier(0);
+      load_strips(pp_clampi(nxt + 2, 0, d.nz - 1));
+      __builtin_amdgcn_sched_barrier(0);
+    } else {
+      if (fresh_next) publish();
+    }
     if (fresh_cur) fused2_xpass<R, NXI, 3 * G::XI>(s_u, s_x, a.wx, xsrc, xdst);
     if (fresh_cur || fresh_next) __syncthreads();
     // ---- interval 2: y pass of plane `cur` (s_x -> registers) | ESM update of plane `nxt` (s_mf -> s_u) ----
@@ -1241,7 +1333,7 @@ __device__ __forceinline__ void fused2_force_body(const float* __restrict__ F, c
     // pending: the image planes are consumed by the next ESM pass, D (SUM) by the next stores.
     {
       const int nxt2 = pp_clampi(zi + 2, 0, d.nz - 1);
-      if (MASK || ((n + 2 < nsteps) && (nxt2 != nxt))) prefetch(nxt2);   // (MASK: a step that would not load re-reads the planes it holds)
+      if (!STRIPS && (MASK || ((n + 2 < nsteps) && (nxt2 != nxt)))) prefetch(nxt2);   // (MASK: a step that would not load re-reads the planes it holds)
     }
     if constexpr (SUM) load_dsum(zo + 1);
     if constexpr (MASK) pp_pairprio_step(yprio, n);
@@ -1273,14 +1365,14 @@ __global__ void __launch_bounds__(512, GEN2_WAVES) k_fused2_force_smooth(const f
   if constexpr (SH == 2) {
     using L0 = fused2_force_lds<R, 0>;
     using L1 = fused2_force_lds<R, 1>;
-    __shared__ __attribute__((aligned(16))) float2 s_mf_[(L0::SZ_IMG2 > L1::SZ_IMG2 ? L0::SZ_IMG2 : L1::SZ_IMG2) / 2];
+    __shared__ __attribute__((aligned(16))) float2 s_mf_[(fused2_force_strips<R, MASK>::value ? 2 : 1) * (L0::SZ_IMG2 > L1::SZ_IMG2 ? L0::SZ_IMG2 : L1::SZ_IMG2) / 2];
     __shared__ __attribute__((aligned(16))) float s_u_[L0::SZ_U > L1::SZ_U ? L0::SZ_U : L1::SZ_U];
     __shared__ __attribute__((aligned(16))) float s_x_[L0::SZ_XT > L1::SZ_XT ? L0::SZ_XT : L1::SZ_XT];
     if (fused_region(a) == 0) fused2_force_body<R, 0, UNROLL, SUM, NT, MASK, BIG>(F, Mw, D, Us, a, K, partials, st, prev, nprev, max_rms, s_mf_, s_u_, s_x_, 0);
     else fused2_force_body<R, 1, UNROLL, SUM, NT, MASK, BIG>(F, Mw, D, Us, a, K, partials, st, prev, nprev, max_rms, s_mf_, s_u_, s_x_, 1);
   } else {
     using L = fused2_force_lds<R, SH>;
-    __shared__ __attribute__((aligned(16))) float2 s_mf_[L::SZ_IMG2 / 2];
+    __shared__ __attribute__((aligned(16))) float2 s_mf_[(fused2_force_strips<R, MASK>::value ? 2 : 1) * L::SZ_IMG2 / 2];
     __shared__ __attribute__((aligned(16))) float s_u_[L::SZ_U];
     __shared__ __attribute__((aligned(16))) float s_x_[L::SZ_XT];
     fused2_force_body<R, SH, UNROLL, SUM, NT, MASK, BIG>(F, Mw, D, Us, a, K, partials, st, prev, nprev, max_rms, s_mf_, s_u_, s_x_, 0);
