@@ -309,6 +309,38 @@ int pp_patch_correlation_f32(pp_ctx* ctx, const float* target, const float* movi
 int pp_joint_histogram_f32(pp_ctx* ctx, const float* a, const float* b, size_t n, int bins_a, int bins_b, int64_t* hist,
                            double range[4]);
 
+/* ---- dose-volume histograms and dose metrics --------------------------------------- */
+typedef struct {
+  int64_t count;     /* voxels with label != 0                                                              */
+  int64_t mask_sum;  /* sum of the label's own values there (a 0 / 255 mask counts 255 per voxel)           */
+  double dose_sum;   /* the exact sum of the fp32 doses there, rounded to fp64 once                         */
+  float dose_min;    /* +inf / -inf for an empty label                                                      */
+  float dose_max;
+} pp_dose_stats;
+/* np.histogram(dose[label_l != 0], bins=edges) for l = 0 ... nlabels - 1 in one pass over the volume (imaging/dose/dvh.py),
+ * and each label's statistics.  labels: host array of nlabels (1 ... 64) device pointers to n uint8 voxels each, non-zero =
+ * inside.  edges: nbins + 1 (nbins 1 ... 2^20) HOST doubles that do not decrease; the last one may be +inf.  hist (HOST,
+ * int64 [nlabels][nbins]): a voxel is counted in the bin with edges[k] <= v < edges[k + 1], the last bin closed on the
+ * right, values outside the edges dropped, the fp32 dose compared as a double -- exactly numpy's counts.  stats (HOST,
+ * nlabels records, or NULL) covers every voxel of a label, including those the histogram dropped.  More labels or bins than
+ * that, or 2^31 voxels or more: PP_ERR_SIZE.  A NaN dose inside any label is an error (PP_ERR_ARG; numpy would return a NaN
+ * mean); NaNs outside every label are never looked at.  Only integer atomics are used (the dose sum is accumulated exactly,
+ * as a 288-bit integer): a rerun gives the same bits.  Per-workgroup LDS tables for as many labels at a time as fit 12288
+ * counters (at most 16; one launch per group of labels), global integer atomics when nbins > 12288.  Synchronises. */
+int pp_dose_histogram_f32(pp_ctx* ctx, const float* dose, const uint8_t* const* labels, int nlabels, size_t n,
+                          const double* edges, int nbins, int64_t* hist, pp_dose_stats* stats);
+/* out[j] (HOST) = the ranks[j]-th smallest (0-based) dose among the voxels with label != 0, bit for bit the fp32 value
+ * np.partition puts there (-0.0 sorts below +0.0), for 1 ... 8 ranks: a radix select in three counting passes of 11 + 11 + 10
+ * bits over the order-preserving integer image of the value; nothing is sorted or copied.  An empty label, a rank outside
+ * [0, count) or a NaN inside the label: PP_ERR_ARG.  Synchronises. */
+int pp_masked_order_stats_f32(pp_ctx* ctx, const float* dose, const uint8_t* label, size_t n, const int64_t* ranks,
+                              int nranks, float* out);
+/* counts[l][j] (HOST, int64 [nlabels][nthresholds]) = voxels of label l with dose >= thresholds[j], compared in fp32, for
+ * every pair in one pass (pp_dose_histogram_f32 over the sorted thresholds with an open top bin).  nthresholds 1 ... 2^20;
+ * a NaN threshold, or a NaN dose inside a label: PP_ERR_ARG.  Synchronises. */
+int pp_masked_count_ge_f32(pp_ctx* ctx, const float* dose, const uint8_t* const* labels, int nlabels, size_t n,
+                           const float* thresholds, int nthresholds, int64_t* counts);
+
 /* ---- iterative atlas removal ------------------------------------------------------- */
 /* sitk.LabelContour(mask) with face connectivity (label/projection.py:85): object voxels that have a face
  * neighbour of a different value. */

@@ -111,6 +111,11 @@ SURFACE_STATS_DTYPE = np.dtype([("count", "<i8"), ("count_le_tau", "<i8"), ("sum
                                 ("max", "<f4"), ("range_lo", "<f4"), ("range_hi", "<f4"), ("hist", "<i8", (SURFACE_BINS,))])
 
 
+DOSE_MAX_LABELS, DOSE_MAX_BINS, ORDER_STATS_MAX_RANKS = 64, 1 << 20, 8
+# pp_dose_stats as a numpy record
+DOSE_STATS_DTYPE = np.dtype([("count", "<i8"), ("mask_sum", "<i8"), ("dose_sum", "<f8"), ("dose_min", "<f4"), ("dose_max", "<f4")])
+
+
 class PlatipyAmdError(RuntimeError):
     pass
 
@@ -163,6 +168,11 @@ _SIGNATURES = {
                                  C.POINTER(StapleResult)]),
     "pp_patch_correlation_f32": (C.c_int, [_P, _P, _P, C.POINTER(C.c_int), C.POINTER(C.c_int), _P]),
     "pp_joint_histogram_f32": (C.c_int, [_P, _P, _P, C.c_size_t, C.c_int, C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_double)]),
+    "pp_dose_histogram_f32": (C.c_int, [_P, _P, C.POINTER(_P), C.c_int, C.c_size_t, C.POINTER(C.c_double), C.c_int,
+                                        C.POINTER(C.c_int64), _P]),
+    "pp_masked_order_stats_f32": (C.c_int, [_P, _P, _P, C.c_size_t, C.POINTER(C.c_int64), C.c_int, C.POINTER(C.c_float)]),
+    "pp_masked_count_ge_f32": (C.c_int, [_P, _P, C.POINTER(_P), C.c_int, C.c_size_t, C.POINTER(C.c_float), C.c_int,
+                                         C.POINTER(C.c_int64)]),
     "pp_label_contour_u8": (C.c_int, [_P, _P, C.POINTER(C.c_int), _P]),
     "pp_distance_map_f32": (C.c_int, [_P, _P, C.POINTER(Geom), C.c_int, C.c_int, _P]),
     "pp_overlap_counts_u8": (C.c_int, [_P, _P, _P, C.c_size_t, C.POINTER(C.c_int64)]),
@@ -509,6 +519,53 @@ class Context:
             raise ValueError(msg.decode(errors="replace") if msg else "pp_joint_histogram_f32: bad argument")
         self._chk(rc, "pp_joint_histogram_f32")
         return hist, tuple(rng)
+
+    # -- dose ---------------------------------------------------------------------
+    def _chk_value(self, rc, what):
+        """ValueError for an argument the library refuses (PP_ERR_ARG, PP_ERR_SIZE), PlatipyAmdError for anything else."""
+        if rc in (ERR_ARG, ERR_SIZE):
+            msg = self.lib.pp_last_error(self.h)
+            raise ValueError(msg.decode(errors="replace") if msg else f"{what}: bad argument")
+        self._chk(rc, what)
+
+    def dose_histogram(self, dose, labels, n, edges):
+        """pp_dose_histogram_f32 over the uint8 masks `labels` -> (int64 counts [len(labels), len(edges) - 1], a
+        DOSE_STATS_DTYPE record per label): np.histogram(dose[mask != 0], bins=edges) and count, mask-value sum, dose sum,
+        min and max of each mask (synchronises).  ValueError for a NaN dose inside a mask, more than DOSE_MAX_LABELS labels or
+        DOSE_MAX_BINS bins, edges that decrease."""
+        e = np.ascontiguousarray(edges, dtype=np.float64).reshape(-1)
+        nbins = max(int(e.size) - 1, 0)
+        hist = np.zeros((len(labels), nbins), dtype=np.int64)
+        stats = np.zeros(len(labels), dtype=DOSE_STATS_DTYPE)
+        ptrs = (_P * max(len(labels), 1))(*[ptr(x) for x in labels])
+        rc = self.lib.pp_dose_histogram_f32(self.h, ptr(dose), ptrs, len(labels), int(n), e.ctypes.data_as(C.POINTER(C.c_double)), nbins,
+                                            hist.ctypes.data_as(C.POINTER(C.c_int64)), stats.ctypes.data)
+        self._chk_value(rc, "pp_dose_histogram_f32")
+        return hist, stats
+
+    def masked_order_stats(self, dose, label, n, ranks):
+        """pp_masked_order_stats_f32 -> float32 array: the ranks[j]-th smallest (0-based) dose inside the uint8 mask, any
+        number of ranks (eight per call).  ValueError for an empty mask, a rank >= its count, a NaN inside it."""
+        ranks = [int(r) for r in ranks]
+        out = np.zeros(len(ranks), dtype=np.float32)
+        for k in range(0, len(ranks), ORDER_STATS_MAX_RANKS):
+            part = ranks[k:k + ORDER_STATS_MAX_RANKS]
+            res = (C.c_float * len(part))()
+            rc = self.lib.pp_masked_order_stats_f32(self.h, ptr(dose), ptr(label), int(n), (C.c_int64 * len(part))(*part), len(part), res)
+            self._chk_value(rc, "pp_masked_order_stats_f32")
+            out[k:k + len(part)] = np.frombuffer(res, dtype=np.float32)
+        return out
+
+    def masked_count_ge(self, dose, labels, n, thresholds):
+        """pp_masked_count_ge_f32 -> int64 [len(labels), len(thresholds)]: voxels of each uint8 mask with dose >= threshold,
+        the thresholds rounded to float32 and compared as float32 (synchronises)."""
+        t = np.ascontiguousarray(thresholds, dtype=np.float32).reshape(-1)
+        counts = np.zeros((len(labels), int(t.size)), dtype=np.int64)
+        ptrs = (_P * max(len(labels), 1))(*[ptr(x) for x in labels])
+        rc = self.lib.pp_masked_count_ge_f32(self.h, ptr(dose), ptrs, len(labels), int(n), t.ctypes.data_as(C.POINTER(C.c_float)),
+                                             int(t.size), counts.ctypes.data_as(C.POINTER(C.c_int64)))
+        self._chk_value(rc, "pp_masked_count_ge_f32")
+        return counts
 
     def label_contour(self, mask, size, out):
         self._chk(self.lib.pp_label_contour_u8(self.h, ptr(mask), _i3(size), ptr(out)), "pp_label_contour_u8")

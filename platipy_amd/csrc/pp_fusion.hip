@@ -1944,3 +1944,6 @@ int pp_linear_set_sample_jitter(pp_ctx* ctx, const float* jitter, size_t nsample
 
 // patch correlation and the joint histogram (label/fusion.py:94-132, :26-53): pp_patch_correlation_f32, pp_joint_histogram_f32
 #include "pp_patch_corr.h"
+
+// dose-volume histograms and dose metrics (imaging/dose/): pp_dose_histogram_f32, pp_masked_order_stats_f32, pp_masked_count_ge_f32
+#include "pp_dose.h"
