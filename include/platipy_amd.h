@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define PP_ABI_VERSION 2
+#define PP_ABI_VERSION 3
 
 typedef enum {
   PP_OK = 0,
@@ -41,7 +41,8 @@ typedef enum {
   PP_ERR_ALLOC = -3,       /* workspace allocation failed                         */
   PP_ERR_UNSUPPORTED = -4, /* valid request this build does not implement         */
   PP_ERR_SIZE = -5,        /* volume too small / too large for the operation      */
-  PP_ERR_NO_OVERLAP = -6   /* linear registration: no valid sample point at start */
+  PP_ERR_NO_OVERLAP = -6,  /* linear registration: no valid sample point at start */
+  PP_ERR_DIRECTION = -7    /* B-spline metric: lattice / virtual / fixed direction cosines differ */
 } pp_status;
 
 enum { PP_INTERP_NEAREST = 1, PP_INTERP_LINEAR = 2, PP_INTERP_BSPLINE = 3 }; /* = sitk.sitkNearestNeighbor / sitkLinear / sitkBSpline */
@@ -518,6 +519,40 @@ int pp_linear_optimize_f32(pp_ctx* ctx, const float* fixed, const int fsize[3], 
                            const int msize[3], const uint8_t* fixed_mask, const uint8_t* moving_mask,
                            const pp_linreg_level* level, double* params, pp_linreg_stats* stats,
                            double* history, int history_capacity);
+
+/* ---- cubic B-spline transform (sitk.BSplineTransform, order 3) ---------------------------------------------------
+ * The coefficient lattice is a planar fp32 device array [3][cz][cy][cx] (x, y, z displacement in mm) with its own
+ * geometry `lattice`: size = mesh + 3 per axis, spacing = domain length / mesh, origin one lattice spacing before the
+ * domain origin, direction = the domain's.  A physical point p with continuous lattice index u is inside the transform
+ * domain when 1 <= u < mesh + 1 on every axis; there T(p) = p + sum w_i w_j w_k c_ijk over its 4 x 4 x 4 support, and
+ * T(p) = p everywhere else (itk::BSplineTransform::InsideValidRegion) [ITK-upstream, unverified here]. */
+
+/* Dense evaluation: out = planar displacement field [3][Z][Y][X] of the transform on the grid `grid`
+ * (sitk.TransformToDisplacementField for a B-spline; what apply_transform needs, reference registration/utils.py:176).
+ * The grid may differ from the lattice in size, spacing, origin and direction; voxels outside the domain get exactly 0. */
+int pp_bspline_field_f32(pp_ctx* ctx, const float* coefficients, const pp_geom* lattice, const pp_geom* grid, float* out);
+
+enum { PP_BSPLINE_MEAN_SQUARES = 0, PP_BSPLINE_CORRELATION = 1 };
+/* stats[] of pp_bspline_metric_f32 */
+enum { PP_BSPLINE_STAT_VALID = 0, PP_BSPLINE_STAT_OUTSIDE = 1, PP_BSPLINE_STAT_MASKED = 2, PP_BSPLINE_STAT_SEEN = 3 };
+/* Similarity metric of `fixed` and `moving` under the B-spline and its gradient with respect to all 3 cx cy cz
+ * coefficients, ITK's flat parameter order (what registration_method.Execute evaluates per iteration at reference
+ * deformable.py:513 with the metrics set at deformable.py:533 and before).  Samples are every `stride`-th voxel (raster
+ * order) of the grid `virt`, moved by the jitter installed with pp_linear_set_sample_jitter when there is one; the
+ * moving gradient comes from the image installed with pp_linear_set_moving_gradient(_packed), else from the
+ * trilinear interpolant; masks are uint8 volumes of the fixed / moving size or NULL.  Value and sign conventions are
+ * those of pp_meansq_affine_f32 (sum of squares / count) and pp_corr_moments_affine_f32 combined (-corr^2).
+ *   jitter_bound: an upper bound of |jitter| in virtual voxels, any axis (0 without jitter); a sample that moves
+ *                 further is reported as PP_ERR_ARG, never dropped silently.
+ *   value, stats[4] (valid samples, samples outside the fixed or moving buffer, samples rejected by a mask, samples
+ *   visited), gradient[3 cx cy cz]: HOST memory.  No valid sample: PP_ERR_NO_OVERLAP.
+ * The direction cosines of `lattice`, `virt` and `fixed_geom` must agree (the initialiser takes them from the fixed
+ * image): PP_ERR_DIRECTION otherwise, before anything is launched.  Two calls on the same inputs return identical bits.
+ * Synchronises. */
+int pp_bspline_metric_f32(pp_ctx* ctx, int metric, const float* fixed, const pp_geom* fixed_geom, const float* moving,
+                          const pp_geom* moving_geom, const pp_geom* virt, int stride, const uint8_t* fixed_mask,
+                          const uint8_t* moving_mask, const float* coefficients, const pp_geom* lattice,
+                          double jitter_bound, double* value, double* stats, double* gradient);
 
 #ifdef __cplusplus
 }

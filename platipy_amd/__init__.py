@@ -29,6 +29,7 @@ if "GPU_MAX_HW_QUEUES" not in _os.environ:
 from .image import Image, image_from_array, array_from_image  # noqa: E402,F401
 from .transform import (  # noqa: E402,F401
     AffineTransform,
+    BSplineTransform,
     CompositeTransform,
     DisplacementFieldTransform,
     Euler3DTransform,
@@ -38,6 +39,7 @@ from .transform import (  # noqa: E402,F401
     Transform,
     TranslationTransform,
     VersorRigid3DTransform,
+    bspline_transform_initializer,
     sitkBSpline,
     sitkLinear,
     sitkNearestNeighbor,

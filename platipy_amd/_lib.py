@@ -18,7 +18,7 @@ INTERP_NEAREST = 1
 INTERP_LINEAR = 2
 INTERP_BSPLINE = 3
 DEMONS_AUTO, DEMONS_STAGED, DEMONS_FUSED = 0, 1, 2
-ABI_VERSION = 2
+ABI_VERSION = 3
 HISTORY_CAPACITY = 4096     # PP_DEMONS_HISTORY_CAPACITY: iterations of one Execute whose metric / RMS change the device ring keeps
 
 
@@ -51,6 +51,8 @@ class LinregStats(C.Structure):     # pp_linreg_stats
 
 ERR_ARG, ERR_SIZE = -1, -5
 ERR_NO_OVERLAP = -6
+ERR_DIRECTION = -7
+BSPLINE_MEAN_SQUARES, BSPLINE_CORRELATION = 0, 1
 MODEL_TRANSLATION, MODEL_VERSOR_RIGID, MODEL_SIMILARITY, MODEL_SCALE, MODEL_AFFINE, MODEL_EULER, MODEL_SCALE_VERSOR, MODEL_SCALE_SKEW_VERSOR = range(8)
 OPT_GD, OPT_GD_LINE_SEARCH = 0, 1
 LINREG_RETURN_BEST = 1
@@ -204,6 +206,10 @@ _SIGNATURES = {
     "pp_reload_switches": (None, []),
     "pp_linear_optimize_f32": (C.c_int, [_P, _P, C.POINTER(C.c_int), _P, C.POINTER(C.c_int), _P, _P, C.POINTER(LinregLevel),
                                          C.POINTER(C.c_double), C.POINTER(LinregStats), C.POINTER(C.c_double), C.c_int]),
+    "pp_bspline_field_f32": (C.c_int, [_P, _P, C.POINTER(Geom), C.POINTER(Geom), _P]),
+    "pp_bspline_metric_f32": (C.c_int, [_P, C.c_int, _P, C.POINTER(Geom), _P, C.POINTER(Geom), C.POINTER(Geom), C.c_int, _P, _P, _P,
+                                        C.POINTER(Geom), C.c_double, C.POINTER(C.c_double), C.POINTER(C.c_double),
+                                        C.POINTER(C.c_double)]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
@@ -398,6 +404,37 @@ class Context:
         tt = (C.c_double * 3)(*[float(v) for v in np.asarray(t, dtype=np.float64).ravel()])
         self._chk(self.lib.pp_transform_to_field_f32(self.h, C.byref(geom), a, tt, ptr(add_field) if add_field is not None else None,
                                                      ptr(out)), "pp_transform_to_field_f32")
+
+    def bspline_field(self, coefficients, lattice_geom, grid_geom, out):
+        """Displacement field [3, Z, Y, X] of a cubic B-spline transform (coefficients [3, cz, cy, cx] on `lattice_geom`) on the
+        grid `grid_geom`; exactly 0 outside the transform domain (pp_bspline_field_f32)."""
+        self._chk(self.lib.pp_bspline_field_f32(self.h, ptr(coefficients), C.byref(lattice_geom), C.byref(grid_geom), ptr(out)),
+                  "pp_bspline_field_f32")
+
+    def bspline_metric(self, metric, fixed, fixed_geom, moving, moving_geom, virtual_geom, stride, coefficients, lattice_geom,
+                       fixed_mask=None, moving_mask=None, jitter_bound=0.0):
+        """pp_bspline_metric_f32 -> (value, float64 gradient [3 cx cy cz] in ITK's parameter order, stats dict).  Raises
+        PlatipyAmdError with .code (ERR_DIRECTION, ERR_NO_OVERLAP, ...)."""
+        n = 3 * int(lattice_geom.size[0]) * int(lattice_geom.size[1]) * int(lattice_geom.size[2])
+        for what, buf, g, width in (("fixed", fixed, fixed_geom, 4), ("moving", moving, moving_geom, 4), ("fixed_mask", fixed_mask, fixed_geom, 1),
+                                    ("moving_mask", moving_mask, moving_geom, 1), ("coefficients", coefficients, lattice_geom, 12)):
+            # the library gets bare pointers: a buffer that does not have its geometry's size would be read past its end
+            have = None if buf is None or isinstance(buf, int) else (buf.numel() * buf.element_size() if hasattr(buf, "numel") else buf.nbytes)
+            if have is not None and have != width * int(g.size[0]) * int(g.size[1]) * int(g.size[2]):
+                raise ValueError(f"bspline_metric: `{what}` does not have the size of its geometry")
+        grad = np.zeros(n, dtype=np.float64)
+        value = C.c_double()
+        st = (C.c_double * 4)()
+        rc = self.lib.pp_bspline_metric_f32(self.h, int(metric), ptr(fixed), C.byref(fixed_geom), ptr(moving), C.byref(moving_geom),
+                                            C.byref(virtual_geom), int(stride), ptr(fixed_mask), ptr(moving_mask), ptr(coefficients),
+                                            C.byref(lattice_geom), float(jitter_bound), C.byref(value), st,
+                                            grad.ctypes.data_as(C.POINTER(C.c_double)))
+        if rc:
+            msg = self.lib.pp_last_error(self.h)
+            err = PlatipyAmdError(f"pp_bspline_metric_f32 failed ({rc}): {msg.decode(errors='replace') if msg else ''}")
+            err.code = rc
+            raise err
+        return value.value, grad, {"valid": st[0], "outside": st[1], "masked": st[2], "seen": st[3]}
 
     def compose_field(self, total, it, geom):
         self._chk(self.lib.pp_compose_field_f32(self.h, ptr(total), ptr(it), C.byref(geom)), "pp_compose_field_f32")

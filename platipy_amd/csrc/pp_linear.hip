@@ -567,3 +567,6 @@ extern "C" int pp_linear_optimize_f32(pp_ctx* ctx, const float* fixed, const int
   }
   return PP_OK;
 }
+
+// ---- cubic B-spline transform: dense evaluation, metric and gradient over the control-point lattice ------------------
+#include "pp_bspline.h"

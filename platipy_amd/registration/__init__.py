@@ -1,10 +1,13 @@
 from .deformable import fast_symmetric_forces_demons_registration, multiscale_demons, HipDemonsFilter  # noqa: F401
+from .bspline import bspline_registration, refine_bspline  # noqa: F401
 from .linear import linear_registration  # noqa: F401
 from .utils import (  # noqa: F401
     apply_deformable_transform,
     apply_linear_transform,
     apply_transform,
     convert_mask_to_distance_map,
+    control_point_spacing_distance_to_number,
     convert_mask_to_reg_structure,
     smooth_and_resample,
+    transform_to_displacement_field,
 )

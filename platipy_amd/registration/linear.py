@@ -723,6 +723,61 @@ def itk_moving_gradient(ctx, moving):
     return mixed
 
 
+def gradient_descent_level(value_and_gradient, values, value, update, scales, step_scale, params, opt, number_of_iterations,
+                           max_step, verbose=False, return_best_parameters=False, record=None):
+    """One level of itk::GradientDescentOptimizerv4 / GradientDescentLineSearchOptimizerv4 over any number of parameters
+    (the <= 15 of a linear model, the thousands of a B-spline lattice): gradient divided by `scales`, learning rate estimated
+    once so that the first step moves the domain by `max_step` (step_scale(params, step) = the physical shift `step` causes),
+    optional golden-section search on [0, 5] x learning rate, ITK's window convergence test, the LAST point returned unless
+    `return_best_parameters`.  The callables: value_and_gradient(p) -> (v, g) and value(p) raise RuntimeError off the overlap,
+    values([p, ...]) -> list of values (+inf off the overlap), update(p, step) = UpdateTransformParameters."""
+    learning_rate = 1.0
+    history = []
+    best_value, best_params = float("inf"), params.copy()
+    previous, stop = params.copy(), 0
+    for it in range(number_of_iterations):
+        try:
+            value_, grad = value_and_gradient(params)
+        except RuntimeError:
+            if it == 0:
+                raise
+            params, stop = previous, 2                      # stepped off the overlap: the level ends at the last point with samples
+            break
+        if value_ < best_value:
+            best_value, best_params = value_, params.copy()
+        history.append(value_)
+        if verbose:
+            print("{0:3} = {1:10.5f}".format(it, value_))
+        if _window_convergence(history, 10) <= 1e-6:
+            stop = 1
+            break
+        g = grad / scales                                   # ModifyGradientByScales
+        if it == 0:                                         # estimateLearningRate = Once (per StartOptimization: per level)
+            ss = step_scale(params, -g)
+            learning_rate = max_step / ss if ss > np.finfo(np.float64).eps else 1.0
+        if opt == "gradient_descent_line_search":
+            base = params.copy()
+
+            def trial(es):
+                return values([update(base, -e * g) for e in es])
+
+            lr = _golden_section(trial, 0.0, learning_rate, 5.0 * learning_rate)
+            learning_rate = lr if lr > 0 else learning_rate
+        previous = params
+        params = update(params, -learning_rate * g)         # m_Metric->UpdateTransformParameters(m_Gradient)
+    if return_best_parameters:
+        try:
+            last = value(params)
+        except RuntimeError:
+            last = float("inf")
+        if last > best_value:
+            params = best_params
+    if record is not None:
+        record.append({"values": list(history), "iterations": len(history), "stop": stop, "learning_rate": float(learning_rate),
+                       "parameters": [float(v) for v in params]})
+    return params
+
+
 def _level_args(scope):
     keys = ("fixed_image", "moving_image", "fixed_mask", "moving_mask", "initial_transform", "model", "params", "metric", "opt",
             "shrink_factors", "smooth_sigmas", "sampling_rate", "number_of_iterations", "verbose", "exhaustive_steps",
@@ -795,50 +850,9 @@ def _optimise_levels(ctx, jitter, fixed_image, moving_image, fixed_mask, moving_
                                             record)
             continue
 
-        scales = ms.scales(model, params)
-        learning_rate = 1.0
-        history = []
-        best_value, best_params = float("inf"), params.copy()
-        previous, stop = params.copy(), 0
-        for it in range(number_of_iterations):
-            try:
-                value, grad = ms.value_and_gradient(model, params)
-            except RuntimeError:
-                if it == 0:
-                    raise
-                params, stop = previous, 2                      # stepped off the overlap: the level ends at the last point with samples
-                break
-            if value < best_value:
-                best_value, best_params = value, params.copy()
-            history.append(value)
-            if verbose:
-                print("{0:3} = {1:10.5f}".format(it, value))
-            if _window_convergence(history, 10) <= 1e-6:
-                stop = 1
-                break
-            g = grad / scales                                   # ModifyGradientByScales
-            if it == 0:                                         # estimateLearningRate = Once (per StartOptimization: per level)
-                ss = ms.step_scale(model, params, -g)
-                learning_rate = max_step / ss if ss > np.finfo(np.float64).eps else 1.0
-            if opt == "gradient_descent_line_search":
-                base = params.copy()
-
-                def trial(es):
-                    return ms.values(model, [model.update(base, -e * g) for e in es])
-
-                lr = _golden_section(trial, 0.0, learning_rate, 5.0 * learning_rate)
-                learning_rate = lr if lr > 0 else learning_rate
-            previous = params
-            params = model.update(params, -learning_rate * g)   # m_Metric->UpdateTransformParameters(m_Gradient)
-        if return_best_parameters:
-            try:
-                last = ms.value(model, params)
-            except RuntimeError:
-                last = float("inf")
-            if last > best_value:
-                params = best_params
-        if record is not None:
-            record.append({"values": list(history), "iterations": len(history), "stop": stop, "learning_rate": float(learning_rate),
-                           "parameters": [float(v) for v in params]})
+        params = gradient_descent_level(
+            lambda p: ms.value_and_gradient(model, p), lambda plist: ms.values(model, plist), lambda p: ms.value(model, p),
+            model.update, ms.scales(model, params), lambda p, step: ms.step_scale(model, p, step), params, opt,
+            number_of_iterations, max_step, verbose, return_best_parameters, record)
 
     return params

@@ -11,6 +11,7 @@ from .. import _lib
 from ..image import Image, as_image, cast_tensor
 from .. import runtime
 from ..transform import (
+    BSplineTransform,
     CompositeTransform,
     DisplacementFieldTransform,
     Transform,
@@ -29,12 +30,26 @@ def _check_interp(interpolator):
     return {sitkNearestNeighbor: _lib.INTERP_NEAREST, sitkLinear: _lib.INTERP_LINEAR, sitkBSpline: _lib.INTERP_BSPLINE}[interpolator]
 
 
+def control_point_spacing_distance_to_number(image, grid_spacing):
+    """Grid spacing in mm -> number of B-spline mesh cells per axis (reference registration/utils.py:44-51)."""
+    number_points = np.array(image.GetSize()) * np.array(image.GetSpacing()) / np.array(grid_spacing)
+    return (number_points + 0.5).astype(int)
+
+
+def _bspline_as_field(transform, reference):
+    """A BSplineTransform as the DisplacementFieldTransform of its dense evaluation on `reference`'s grid
+    (pp_bspline_field_f32): how every path below takes one, alone or as any member of a composite."""
+    field = transform.displacement_field(reference)
+    return DisplacementFieldTransform(Image(field, reference.spacing, reference.origin, reference.direction, True))
+
+
 def _split_transform(transform, reference):
     """-> (A, t, field_tensor_on_reference_grid or None) such that q = A p + t + field(p)."""
     if transform is None or type(transform) is Transform:
         return None, None, None
     parts = transform.flatten() if isinstance(transform, CompositeTransform) else [transform]
     parts = [p for p in parts if type(p) is not Transform]
+    parts = [_bspline_as_field(p, reference) if isinstance(p, BSplineTransform) else p for p in parts]
     fields = [i for i, p in enumerate(parts) if isinstance(p, DisplacementFieldTransform)]
     if not fields:
         A, off = CompositeTransform(parts).matrix_offset()
@@ -60,6 +75,7 @@ def _total_field(parts, reference):
     """D(p) = T(p) - p on `reference`'s grid for T = parts[0] o parts[1] o ... (the LAST member is applied first), members
     linear or displacement-field transforms in any order.  A field member F maps q -> q + F(q), with F interpolated
     linearly on ITS grid and zero outside it (itk::DisplacementFieldTransform); the running map is kept as p + D(p)."""
+    parts = [_bspline_as_field(p, reference) if isinstance(p, BSplineTransform) else p for p in parts]
     ctx = runtime.context(reference.device)
     geom = reference.geom()
     A, off, D = np.eye(3), np.zeros(3), None        # pending linear map q = A p + off while no field has been applied yet

@@ -281,3 +281,130 @@ class Euler3DTransform(_Parametrised):
         Ry = np.array([[cy, 0, sy], [0, 1, 0], [-sy, 0, cy]])
         Rz = np.array([[cz, -sz, 0], [sz, cz, 0], [0, 0, 1]])
         return Rz @ Rx @ Ry, np.asarray(p[3:6], dtype=np.float64).copy()
+
+
+# --------------------------------------------------------------------------------------
+# cubic B-spline (free-form deformation) transform, reference registration/deformable.py:513
+
+
+class BSplineTransform(Transform):
+    """sitk.BSplineTransform(3, order 3): q = p + sum w_i(u) w_j(v) w_k(w) c_ijk over the 4 x 4 x 4 control points around p
+    inside the transform domain, q = p outside it (itk::BSplineTransform::InsideValidRegion) [ITK-upstream, unverified here].
+
+    The coefficients live in HBM as one planar fp32 tensor [3, cz, cy, cx] (x, y, z displacement in mm; the lattice has
+    mesh + 3 control points per axis).  GetParameters / SetParameters use ITK's flat order: all x coefficients, then y, then
+    z, each block x fastest over the lattice -- which is this tensor's memory order."""
+
+    def __init__(self, transform_domain_mesh_size, transform_domain_origin=(0.0, 0.0, 0.0),
+                 transform_domain_physical_dimensions=(1.0, 1.0, 1.0), transform_domain_direction=(1, 0, 0, 0, 1, 0, 0, 0, 1),
+                 coefficients=None, device=None):
+        import torch
+
+        self.mesh_size = tuple(int(m) for m in transform_domain_mesh_size)
+        if len(self.mesh_size) != 3 or min(self.mesh_size) < 1:
+            raise ValueError("BSplineTransform: the mesh needs at least one cell on each of three axes")
+        self.domain_origin = tuple(float(v) for v in transform_domain_origin)
+        self.domain_dimensions = tuple(float(v) for v in transform_domain_physical_dimensions)
+        self.domain_direction = tuple(float(v) for v in transform_domain_direction)
+        cx, cy, cz = (m + 3 for m in self.mesh_size)
+        if coefficients is None:
+            if device is None:
+                from . import runtime
+
+                device = runtime.default_device()
+            coefficients = torch.zeros((3, cz, cy, cx), dtype=torch.float32, device=device)
+        if tuple(coefficients.shape) != (3, cz, cy, cx):
+            raise ValueError(f"BSplineTransform: coefficients must be [3, {cz}, {cy}, {cx}]")
+        self.coefficients = coefficients.to(torch.float32).contiguous()
+
+    # -- SimpleITK's accessors -------------------------------------------------------
+    def GetOrder(self):
+        return 3
+
+    def GetDimension(self):
+        return 3
+
+    def GetTransformDomainMeshSize(self):
+        return self.mesh_size
+
+    def GetTransformDomainOrigin(self):
+        return self.domain_origin
+
+    def GetTransformDomainPhysicalDimensions(self):
+        return self.domain_dimensions
+
+    def GetTransformDomainDirection(self):
+        return self.domain_direction
+
+    def GetNumberOfParameters(self):
+        return int(self.coefficients.numel())
+
+    def GetParameters(self):
+        return tuple(float(v) for v in self.coefficients.detach().reshape(-1).cpu().numpy())
+
+    def SetParameters(self, params):
+        import torch
+
+        p = np.asarray(params, dtype=np.float32).reshape(-1)
+        if p.size != self.coefficients.numel():
+            raise ValueError(f"BSplineTransform: {self.coefficients.numel()} parameters expected, {p.size} given")
+        self.coefficients = torch.from_numpy(p.reshape(tuple(self.coefficients.shape)).copy()).to(self.coefficients.device)
+
+    def GetCoefficientImages(self):
+        """Three scalar Images [cz, cy, cx] on the lattice's own geometry (x, y, z displacement coefficients)."""
+        from .image import Image
+
+        sp, org = self.lattice_spacing(), self.lattice_origin()
+        return tuple(Image(self.coefficients[c].clone(), sp, org, self.domain_direction) for c in range(3))
+
+    # -- lattice geometry --------------------------------------------------------------
+    def lattice_size(self):
+        return tuple(m + 3 for m in self.mesh_size)
+
+    def lattice_spacing(self):
+        return tuple(d / m for d, m in zip(self.domain_dimensions, self.mesh_size))
+
+    def lattice_origin(self):
+        """One lattice spacing before the domain origin along each axis."""
+        D = np.asarray(self.domain_direction, dtype=np.float64).reshape(3, 3)
+        return tuple(np.asarray(self.domain_origin) - D @ np.asarray(self.lattice_spacing()))
+
+    def lattice_geom(self):
+        from . import _lib
+
+        return _lib.make_geom(self.lattice_size(), self.lattice_spacing(), self.lattice_origin(), self.domain_direction)
+
+    def is_linear(self):
+        return False
+
+    def matrix_offset(self):
+        raise TypeError("a BSplineTransform has no matrix / offset form")
+
+    def displacement_field(self, reference):
+        """D(p) = T(p) - p on `reference`'s grid as a planar fp32 tensor [3, Z, Y, X] (pp_bspline_field_f32)."""
+        import torch
+
+        from . import runtime
+
+        ctx = runtime.context(self.coefficients.device)
+        out = torch.empty((3,) + tuple(reference.shape), dtype=torch.float32, device=self.coefficients.device)
+        ctx.bspline_field(self.coefficients, self.lattice_geom(), reference.geom(), out)
+        return out
+
+    def __repr__(self):
+        return (f"BSplineTransform(mesh={self.mesh_size}, origin={self.domain_origin}, dimensions={self.domain_dimensions}, "
+                f"direction={self.domain_direction})")
+
+
+def bspline_transform_initializer(image, transform_domain_mesh_size, device=None):
+    """sitk.BSplineTransformInitializer(image, transformDomainMeshSize) [ITK-upstream, unverified here]: the transform domain is
+    the image's physical box, continuous index -0.5 .. size - 0.5 on each axis, with the image's direction; zero coefficients."""
+    size = np.asarray(image.GetSize(), dtype=np.float64)
+    sp = np.asarray(image.GetSpacing(), dtype=np.float64)
+    D = np.asarray(image.GetDirection(), dtype=np.float64).reshape(3, 3)
+    origin = np.asarray(image.GetOrigin(), dtype=np.float64) + D @ (-0.5 * sp)
+    if device is None:
+        device = getattr(image, "device", None)
+        if device is not None and str(device) == "meta":
+            device = None
+    return BSplineTransform([int(m) for m in transform_domain_mesh_size], origin, size * sp, D.ravel(), device=device)
