@@ -62,21 +62,23 @@ __global__ void __launch_bounds__(NT) k_contour6(const uint8_t* __restrict__ mas
   }
 }
 
-// Pass 1: squared distance (mm^2) to the nearest border voxel along z, per (x, y) column.
+// Pass 1: squared distance (mm^2) to the nearest border voxel along z, per (x, y) column.  The distance is the voxel
+// count times the spacing, rounded once: adding the spacing voxel by voxel rounds at every step, always the same way
+// while the sum stays in one binade, and was 3e-6 off after 1000 voxels of 0.3 mm.
 __global__ void __launch_bounds__(NT) k_edt_z(const uint8_t* __restrict__ border, float* __restrict__ d2, pp_dims d, float sz_mm) {
   const size_t ncol = (size_t)d.nx * d.ny;
   for (size_t c = (size_t)blockIdx.x * NT + threadIdx.x; c < ncol; c += (size_t)gridDim.x * NT) {
-    float run = BIG;  // distance (mm) to the last border voxel seen
+    int run = -1;  // voxels since the last border voxel seen; -1: none yet
     for (int z = 0; z < d.nz; ++z) {
       const size_t i = (size_t)z * ncol + c;
-      run = border[i] ? 0.0f : (run < BIG ? run + sz_mm : BIG);
-      d2[i] = run;
+      run = border[i] ? 0 : (run >= 0 ? run + 1 : -1);
+      d2[i] = run >= 0 ? (float)run * sz_mm : BIG;
     }
-    run = BIG;
+    run = -1;
     for (int z = d.nz - 1; z >= 0; --z) {
       const size_t i = (size_t)z * ncol + c;
-      run = border[i] ? 0.0f : (run < BIG ? run + sz_mm : BIG);
-      const float m = fminf(d2[i], run);
+      run = border[i] ? 0 : (run >= 0 ? run + 1 : -1);
+      const float m = fminf(d2[i], run >= 0 ? (float)run * sz_mm : BIG);
       d2[i] = m < BIG ? m * m : BIG;
     }
   }

@@ -184,3 +184,89 @@ def record_stats(name, stats):
             json.dump(stats, fh, indent=1, sort_keys=True, default=float)
     except OSError:
         pass
+
+
+# --------------------------------------------------------------------------------------
+# adversarial binary volumes for the mask post-processing kernels (tests/test_mask_kernels.py); all [Z][Y][X] uint8
+
+
+def serpentine(shape):
+    """A one-voxel-wide snake: full x-rows at every other y, joined by single voxels at alternating x ends; the same
+    pattern on every other z, the planes joined by single voxels alternately at the pattern's end and at its start.  One
+    face-connected component whose last voxel is (rows x nx) voxels along the path from voxel 0."""
+    nz, ny, nx = shape
+    plane = np.zeros((ny, nx), np.uint8)
+    plane[0::2, :] = 1
+    for k, y in enumerate(range(1, ny - 1, 2)):
+        plane[y, nx - 1 if k % 2 == 0 else 0] = 1
+    last_row = (ny - 1) // 2 * 2
+    end = (last_row, 0 if (last_row // 2) % 2 else nx - 1)     # where the path that starts at (0, 0) leaves the plane
+    m = np.zeros(shape, np.uint8)
+    m[0::2] = plane
+    for k, z in enumerate(range(1, nz - 1, 2)):
+        y, x = end if k % 2 == 0 else (0, 0)
+        m[z, y, x] = 1
+    return m
+
+
+def checkerboard(shape):
+    zz, yy, xx = np.indices(shape)
+    return ((zz + yy + xx) % 2 == 0).astype(np.uint8)
+
+
+def nested_shells(shape=(13, 14, 15), opening=None):
+    """A hollow box (walls one voxel thick, one voxel inside the volume) holding a hollow box holding a solid.
+    opening: None, or 'face' / 'edge' / 'corner': one wall voxel removed so that the outer cavity touches the outside
+    across a face (no longer a hole), or only across an edge / a corner (still a hole under face connectivity)."""
+    m = np.zeros(shape, np.uint8)
+    for k, v in ((1, 1), (2, 0), (4, 1), (5, 0), (6, 1)):
+        m[k:shape[0] - k, k:shape[1] - k, k:shape[2] - k] = v
+    if opening == "face":
+        m[1, shape[1] // 2, shape[2] // 2] = 0
+    elif opening == "edge":
+        m[1, 1, shape[2] // 2] = 0
+    elif opening == "corner":
+        m[1, 1, 1] = 0
+    return m
+
+
+def bernoulli(shape, density, seed):
+    return (np.random.default_rng(seed).random(shape) < density).astype(np.uint8)
+
+
+def random_runs(shape, seed, lo=1, hi=5):
+    """Every x-row alternates foreground and background runs of random length lo..hi, starting with either value."""
+    rng = np.random.default_rng(seed)
+    nz, ny, nx = shape
+    m = np.zeros((nz * ny, nx), np.uint8)
+    for r in range(nz * ny):
+        lens = rng.integers(lo, hi + 1, size=nx // lo + 1)
+        vals = (np.arange(lens.size) + rng.integers(0, 2)) % 2
+        m[r] = np.repeat(vals, lens)[:nx]
+    return m.reshape(shape)
+
+
+def boundary_rows(nx, rows, seed, span=8, pass_len=512):
+    """[rows][nx] rows whose runs straddle the multiples of `span` and of `pass_len` in every way: one run over the whole
+    row; period-3 and period-11 runs; random runs of 1..20; a run that starts in the first pass and ends in the last (the
+    passes between hold no run start); runs of exactly span and pass_len voxels that start one voxel before / on / after
+    each pass boundary; a single last voxel."""
+    rng = np.random.default_rng(seed)
+    x = np.arange(nx)
+    pats = [np.ones(nx, np.uint8), ((x // 3) % 2).astype(np.uint8), (((x + 5) // 11) % 2 == 0).astype(np.uint8),
+            random_runs((1, 1, nx), seed, 1, 20)[0, 0]]
+    long_run = np.zeros(nx, np.uint8)
+    long_run[min(3, nx - 1):max(nx - 2, 1)] = 1
+    pats.append(long_run)
+    edges = np.zeros(nx, np.uint8)
+    for k, b in enumerate(range(pass_len, nx + pass_len, pass_len)):
+        s = b - 1 + k % 3                      # one before, on, one after the boundary
+        edges[s:s + span] = 1
+        edges[max(b - pass_len // 2, 0):max(b - pass_len // 2 + 1, 0)] = 1
+    pats.append(edges)
+    last = np.zeros(nx, np.uint8)
+    last[nx - 1] = 1
+    pats.append(last)
+    pats.append(1 - edges)
+    out = np.stack([pats[(r + int(rng.integers(0, len(pats)))) % len(pats)] if r >= len(pats) else pats[r] for r in range(rows)])
+    return out
