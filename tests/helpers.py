@@ -270,3 +270,76 @@ def boundary_rows(nx, rows, seed, span=8, pass_len=512):
     pats.append(1 - edges)
     out = np.stack([pats[(r + int(rng.integers(0, len(pats)))) % len(pats)] if r >= len(pats) else pats[r] for r in range(rows)])
     return out
+
+
+# --------------------------------------------------------------------------------------
+# geometry and displacement generators for the resampling kernels (tests/test_resample_kernels.py)
+
+EPS6 = 2.0 ** -6
+
+
+def rot_xyz(ax_deg, ay_deg, az_deg):
+    """Proper rotation Rz Ry Rx (degrees about x, y, z)."""
+    ax, ay, az = np.radians([ax_deg, ay_deg, az_deg])
+    rx = np.array([[1, 0, 0], [0, np.cos(ax), -np.sin(ax)], [0, np.sin(ax), np.cos(ax)]])
+    ry = np.array([[np.cos(ay), 0, np.sin(ay)], [0, 1, 0], [-np.sin(ay), 0, np.cos(ay)]])
+    rz = np.array([[np.cos(az), -np.sin(az), 0], [np.sin(az), np.cos(az), 0], [0, 0, 1]])
+    return rz @ ry @ rx
+
+
+def direction_cases():
+    """name -> 3 x 3 direction cosines: identity, a flip of x, the axis permutation (y, z, x) with one sign flipped, a
+    proper rotation by 20 / -35 / 50 degrees about x / y / z, and that rotation times a flip (determinant -1)."""
+    rot = rot_xyz(20.0, -35.0, 50.0)
+    perm = np.array([[0.0, 0.0, 1.0], [1.0, 0.0, 0.0], [0.0, -1.0, 0.0]])    # index x -> physical y, y -> -z, z -> x
+    return {"identity": np.eye(3), "flipx": np.diag([-1.0, 1.0, 1.0]), "perm": perm, "rot": rot,
+            "rotflip": rot @ np.diag([1.0, -1.0, 1.0])}
+
+
+def border_targets(n):
+    """The continuous indices on an axis of n voxels at which a border decision is taken, each with its two neighbours at
+    2^-6: the buffer test's ends -0.5 and n - 0.5, the first and last index, and every nearest-neighbour tie k + 0.5."""
+    t = [-0.5 - EPS6, -0.5, -0.5 + EPS6, -EPS6, 0.0]
+    for k in range(max(n - 1, 1)):
+        t += [k + 0.5 - EPS6, k + 0.5, k + 0.5 + EPS6]
+    t += [n - 1 - EPS6, n - 1.0, n - 1 + EPS6, n - 0.5 - EPS6, n - 0.5, n - 0.5 + EPS6]
+    return t
+
+
+def border_probe_fields(shape, spacing, seed):
+    """Displacement fields [3][Z][Y][X] (physical units, fp32, every value a multiple of 2^-7) on a grid of `shape` with dyadic
+    `spacing` that put the samples of a same-grid gather exactly on border_targets: voxel i of pass p probes axis (i + p N) % 3
+    with the next target of that axis while the other two axes land on multiples of 2^-6 inside [0, n - 1]; every fourth
+    probe puts ALL three axes on a target (corners of the decision).  Consecutive voxels of a row probe different targets,
+    so every row longer than the list holds all of them; shorter volumes get as many passes as it takes for every
+    (axis, target) pair to occur."""
+    rng = np.random.default_rng(seed)
+    nz, ny, nx = shape
+    n = (nx, ny, nz)
+    N = nx * ny * nz
+    tg = [border_targets(k) for k in n]
+    need = 3 * max(len(t) for t in tg)
+    passes = max(1, -(-need // N))
+    z, y, x = np.indices(shape)
+    idx = (x, y, z)
+    lin = (z * ny + y) * nx + x
+    out = []
+    for p in range(passes):
+        q = lin + p * N
+        axis = q % 3
+        c = []
+        for a in range(3):
+            benign = rng.integers(0, (n[a] - 1) * 64 + 1, size=shape) / 64.0
+            probe = np.asarray(tg[a])[(q // 3 + (a * 5)) % len(tg[a])]
+            c.append(np.where((axis == a) | (q % 4 == 3), probe, benign))
+        f = np.stack([(c[a] - idx[a]) * spacing[a] for a in range(3)])
+        assert np.array_equal(f, f.astype(np.float32).astype(np.float64))
+        out.append(f.astype(np.float32))
+    return out
+
+
+def hostile_displacements(spacing_axis):
+    """Physical displacements no volume survives: NaN, +-Inf, +-1e30, +-3e6 voxels, +-(2^23 + 1) voxels."""
+    s = float(spacing_axis)
+    vox = [3.0e6, -3.0e6, 2.0 ** 23 + 1, -(2.0 ** 23 + 1)]
+    return np.array([np.nan, np.inf, -np.inf, 1e30, -1e30] + [v * s for v in vox], dtype=np.float32)
