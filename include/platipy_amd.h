@@ -171,6 +171,18 @@ int pp_resample_f32(pp_ctx* ctx, const float* in, const pp_geom* gin, const pp_g
 int pp_resample_u8(pp_ctx* ctx, const uint8_t* in, const pp_geom* gin, const pp_geom* gout,
                    const double* affine_A, const double* affine_t, const float* field,
                    int interp, double default_value, uint8_t* out);
+/* One fp32 image and nlabels uint8 label volumes, all on the grid gin, through ONE transform onto gout in one gather: what
+ * apply_augmentation (generation/augment.py:65-78) and the atlas propagation (multiatlas/run.py:280-298) do with 1 + M
+ * apply_transform calls.  The field is read, the point mapped, the inside test taken and the sample addresses formed once
+ * per output voxel.  image (may be NULL: labels only) is sampled with image_interp = PP_INTERP_NEAREST or PP_INTERP_LINEAR,
+ * image_default outside, into image_out; labels[l] (HOST array of nlabels device pointers, 0 ... 16) nearest neighbour,
+ * 0 outside, into labels_out[l].  Every output equals, bit for bit, what pp_resample_f32 / pp_resample_u8 return for that
+ * member alone.  PP_INTERP_BSPLINE: PP_ERR_UNSUPPORTED (callers go member by member); more than 16 labels, a negative
+ * count, nothing to resample or an output that aliases its input: PP_ERR_ARG. */
+#define PP_RESAMPLE_SET_MAX_LABELS 16
+int pp_resample_set(pp_ctx* ctx, const pp_geom* gin, const pp_geom* gout, const double* affine_A, const double* affine_t,
+                    const float* field, const float* image, int image_interp, double image_default, float* image_out,
+                    const uint8_t* const* labels, int nlabels, uint8_t* const* labels_out);
 /* itk::BSplineDecompositionImageFilter (spline order 3): samples -> B-spline coefficients, mirror boundaries; `out` may be
  * `in`.  pp_resample_f32 with interp = PP_INTERP_BSPLINE expects this coefficient volume as its input
  * (itk::BSplineInterpolateImageFunction: any sitk interpolator may reach registration/utils.py:176-190). */

@@ -50,6 +50,8 @@ class LinregStats(C.Structure):     # pp_linreg_stats
 
 
 ERR_ARG, ERR_SIZE = -1, -5
+ERR_UNSUPPORTED = -4
+RESAMPLE_SET_MAX_LABELS = 16    # PP_RESAMPLE_SET_MAX_LABELS
 ERR_NO_OVERLAP = -6
 ERR_DIRECTION = -7
 BSPLINE_MEAN_SQUARES, BSPLINE_CORRELATION = 0, 1
@@ -147,6 +149,8 @@ _SIGNATURES = {
                                   _P, C.c_int, C.c_double, _P]),
     "pp_resample_u8": (C.c_int, [_P, _P, C.POINTER(Geom), C.POINTER(Geom), C.POINTER(C.c_double), C.POINTER(C.c_double),
                                  _P, C.c_int, C.c_double, _P]),
+    "pp_resample_set": (C.c_int, [_P, C.POINTER(Geom), C.POINTER(Geom), C.POINTER(C.c_double), C.POINTER(C.c_double), _P, _P, C.c_int,
+                                  C.c_double, _P, C.POINTER(_P), C.c_int, C.POINTER(_P)]),
     "pp_resample_field_f32": (C.c_int, [_P, _P, C.POINTER(Geom), C.POINTER(Geom), _P]),
     "pp_bspline_prefilter_f32": (C.c_int, [_P, _P, C.POINTER(C.c_int), _P]),
     "pp_compose_field_f32": (C.c_int, [_P, _P, _P, C.POINTER(Geom)]),
@@ -389,6 +393,24 @@ class Context:
         fn = self.lib.pp_resample_u8 if u8 else self.lib.pp_resample_f32
         self._chk(fn(self.h, ptr(src), C.byref(gin), C.byref(gout), _dn(affine_A, 9), _dn(affine_t, 3), ptr(field),
                      int(interp), float(default_value), ptr(out)), "pp_resample")
+
+    def resample_set(self, gin, gout, image=None, image_out=None, labels=(), labels_out=(), affine_A=None, affine_t=None, field=None,
+                     interp=INTERP_LINEAR, default_value=0.0):
+        """pp_resample_set: the fp32 `image` (or None) and the uint8 `labels` (at most RESAMPLE_SET_MAX_LABELS), all on `gin`,
+        through one transform onto `gout` in one gather; every output is what `resample` gives for that member alone.  Raises
+        PlatipyAmdError with .code (ERR_UNSUPPORTED for an interpolator the entry declines, ERR_ARG for a bad count)."""
+        if len(labels) != len(labels_out):
+            raise ValueError("resample_set: one output per label")
+        n = len(labels)
+        tin = (_P * max(n, 1))(*[ptr(x) for x in labels])
+        tout = (_P * max(n, 1))(*[ptr(x) for x in labels_out])
+        rc = self.lib.pp_resample_set(self.h, C.byref(gin), C.byref(gout), _dn(affine_A, 9), _dn(affine_t, 3), ptr(field), ptr(image),
+                                      int(interp), float(default_value), ptr(image_out), tin, n, tout)
+        if rc:
+            msg = self.lib.pp_last_error(self.h)
+            err = PlatipyAmdError(f"pp_resample_set failed ({rc}): {msg.decode(errors='replace') if msg else ''}")
+            err.code = rc
+            raise err
 
     def bspline_prefilter(self, src, size, out):
         """B-spline (order 3) coefficients of a fp32 volume (`out` may be `src`)."""

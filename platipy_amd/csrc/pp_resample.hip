@@ -787,6 +787,8 @@ __global__ void __launch_bounds__(NT) k_affine_displacement(pp_dims d, pp_affine
   }
 }
 
+#include "pp_resample_set.h"   // k_resample_set(_axis), resample_set_launch: the kernels above for an image and its labels at once
+
 }  // namespace
 
 int pp_warp_same_grid(pp_ctx* ctx, const float* moving, const float* field, const pp_dims& d, const pp_warp_scale& sc,
@@ -843,6 +845,30 @@ int pp_resample_u8(pp_ctx* ctx, const uint8_t* in, const pp_geom* gin, const pp_
                    const double* affine_t, const float* field, int interp, double default_value, uint8_t* out) {
   pp_device_guard dev_guard_(ctx);
   return resample_any<uint8_t>(ctx, in, gin, gout, affine_A, affine_t, field, interp, default_value, out, "k_resample<u8>");
+}
+
+int pp_resample_set(pp_ctx* ctx, const pp_geom* gin, const pp_geom* gout, const double* affine_A, const double* affine_t,
+                    const float* field, const float* image, int image_interp, double image_default, float* image_out,
+                    const uint8_t* const* labels, int nlabels, uint8_t* const* labels_out) {
+  if (!ctx) return PP_ERR_ARG;
+  pp_device_guard dev_guard_(ctx);
+  PP_REQUIRE(ctx, nlabels >= 0 && nlabels <= PP_RESAMPLE_SET_MAX_LABELS, "pp_resample_set: 0 ... 16 label volumes per call");
+  PP_REQUIRE(ctx, image || nlabels > 0, "pp_resample_set: neither an image nor a label");
+  PP_REQUIRE(ctx, !image || (image_out && image_out != image), "pp_resample_set: NULL or in-place image output");
+  PP_REQUIRE(ctx, nlabels == 0 || (labels && labels_out), "pp_resample_set: NULL label table");
+  if (image && image_interp != PP_INTERP_NEAREST && image_interp != PP_INTERP_LINEAR)
+    return pp_fail(ctx, PP_ERR_UNSUPPORTED, "pp_resample_set: the image interpolator must be nearest or linear; use pp_resample_f32");
+  int rc = pp_geom_check(ctx, gin, "input");
+  if (rc) return rc;
+  rc = pp_geom_check(ctx, gout, "output");
+  if (rc) return rc;
+  rs_set_labels L;
+  for (int l = 0; l < PP_RESAMPLE_SET_MAX_LABELS; ++l) {
+    L.in[l] = l < nlabels ? labels[l] : nullptr;
+    L.out[l] = l < nlabels ? labels_out[l] : nullptr;
+    PP_REQUIRE(ctx, l >= nlabels || (L.in[l] && L.out[l] && L.in[l] != L.out[l]), "pp_resample_set: NULL or in-place label volume");
+  }
+  return resample_set_launch(ctx, gin, gout, affine_A, affine_t, field, image, image_interp, image_default, image_out, L, nlabels);
 }
 
 int pp_bspline_prefilter_f32(pp_ctx* ctx, const float* in, const int size[3], float* out) {

@@ -1,9 +1,25 @@
-"""Drop-in for platipy/imaging/generation/mask.py:107-159 (extend_mask), used by the structure-guided cardiac
-pipeline (projects/cardiac/run.py:741-746, 826-831).  A handful of slice copies on the device tensor."""
+"""Drop-in for platipy/imaging/generation/mask.py: extend_mask (:107-159), used by the structure-guided cardiac
+pipeline (projects/cardiac/run.py:741-746, 826-831) -- a handful of slice copies on the device tensor -- and get_bone_mask
+(:21-47), which generate_random_augmentation needs.  get_external_mask (per-slice convex hulls from scikit-image) has no
+counterpart here."""
 import numpy as np
 import torch
 
 from ..image import as_image
+from ..label.utils import binary_morphological_closing
+
+
+def get_bone_mask(image, lower_threshold=350, upper_threshold=3500, max_hole_size=5):
+    """A binary mask of bones from a CT image (reference mask.py:21-47): sitk.BinaryThreshold on [lower, upper], both ends
+    included, then sitk.BinaryMorphologicalClosing with the ball.  Quirk kept (:41-45): `max_hole_size` is documented as
+    millimetres in z, y, x order but reaches the filter as a kernel radius in VOXELS, x, y, z; False closes nothing."""
+    image = as_image(image)
+    t = image.tensor
+    bone_mask = image.like(((t >= lower_threshold) & (t <= upper_threshold)).to(torch.uint8))
+    if max_hole_size is not False:
+        if not hasattr(max_hole_size, "__iter__"):
+            max_hole_size = (max_hole_size,) * 3
+    return binary_morphological_closing(bone_mask, max_hole_size)
 
 
 def extend_mask(mask, direction=("ax", "sup"), extension_mm=10, interior_mm_shape=10):

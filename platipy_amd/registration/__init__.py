@@ -5,6 +5,7 @@ from .utils import (  # noqa: F401
     apply_deformable_transform,
     apply_linear_transform,
     apply_transform,
+    apply_transform_to_set,
     convert_mask_to_distance_map,
     control_point_spacing_distance_to_number,
     convert_mask_to_reg_structure,

@@ -179,6 +179,62 @@ def apply_transform(input_image, reference_image=None, transform=None, default_v
     return out.like(cast_tensor(out.tensor, original_dtype))
 
 
+def apply_transform_to_set(image, labels, reference_image=None, transform=None, default_value=0, interpolator=sitkLinear):
+    """An image and its structures through ONE transform -> (image_out, [label_out, ...]): what
+    apply_transform(image, reference_image, transform, default_value, interpolator) and, for every label,
+    apply_transform(label, reference_image, transform, 0, sitkNearestNeighbor) return (reference generation/augment.py:65-78,
+    multiatlas/run.py:280-298), bit for bit.  `image` may be None and `labels` empty.
+
+    When the members share one grid, the labels are uint8 and the image interpolator is linear or nearest, the whole set
+    goes through pp_resample_set: the transform is split, the field read and every point mapped once instead of once per
+    member (more than 16 labels: in groups of 16).  Anything else -- sitkBSpline, members on different grids, labels of
+    another type, a uint8 image, a geometry the entry declines -- is the member-by-member path, so a result never depends on
+    which path ran."""
+    image = as_image(image) if image is not None else None
+    labels = [as_image(lab) for lab in labels]
+    members = ([image] if image is not None else []) + labels
+    if not members:
+        return None, []
+    interp = _check_interp(interpolator)
+    first = members[0]
+    fused = (all(m.same_grid(first) and m.device == first.device for m in members)
+             and all(lab.tensor.dtype == torch.uint8 for lab in labels)
+             and (image is None or (interp in (_lib.INTERP_NEAREST, _lib.INTERP_LINEAR) and image.tensor.dtype != torch.uint8)))
+    if fused:
+        try:
+            return _resample_set(image, labels, as_image(reference_image) if reference_image is not None else first, transform,
+                                 default_value, interp)
+        except _lib.PlatipyAmdError as e:
+            if getattr(e, "code", None) != _lib.ERR_UNSUPPORTED:
+                raise
+    image_out = None if image is None else apply_transform(image, reference_image, transform, default_value, interpolator)
+    return image_out, [apply_transform(lab, reference_image, transform, 0, sitkNearestNeighbor) for lab in labels]
+
+
+def _resample_set(image, labels, reference, transform, default_value, interp):
+    first = image if image is not None else labels[0]
+    ctx = runtime.context(first.device)
+    A, t, field = _split_transform(transform, reference)
+    gin, gout = first.geom(), reference.geom()
+    src = out = None
+    if image is not None:
+        src = (image.tensor if image.tensor.dtype == torch.float32 else image.tensor.float()).contiguous()
+        out = torch.empty(reference.shape, dtype=torch.float32, device=src.device)
+    outs = [torch.empty(reference.shape, dtype=torch.uint8, device=first.device) for _ in labels]
+    step = _lib.RESAMPLE_SET_MAX_LABELS
+    for k in range(0, max(len(labels), 1), step):
+        with_image = image is not None and k == 0
+        ctx.resample_set(gin, gout, image=src if with_image else None, image_out=out if with_image else None,
+                         labels=[lab.tensor for lab in labels[k:k + step]], labels_out=outs[k:k + step],
+                         affine_A=None if A is None else A.ravel(), affine_t=None if A is None else t, field=field, interp=interp,
+                         default_value=float(default_value))
+
+    def header(tensor):
+        return Image(tensor, reference.spacing, reference.origin, reference.direction, False)
+
+    return (None if image is None else header(cast_tensor(out, image.tensor.dtype))), [header(o) for o in outs]
+
+
 def apply_linear_transform(input_image, reference_image, transform, is_structure=False, default_value=0,
                            interpolator=sitkNearestNeighbor):
     """registration/utils.py:54-99"""
