@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define PP_ABI_VERSION 3
+#define PP_ABI_VERSION 4
 
 typedef enum {
   PP_OK = 0,
@@ -565,6 +565,30 @@ int pp_bspline_metric_f32(pp_ctx* ctx, int metric, const float* fixed, const pp_
                           const pp_geom* moving_geom, const pp_geom* virt, int stride, const uint8_t* fixed_mask,
                           const uint8_t* moving_mask, const float* coefficients, const pp_geom* lattice,
                           double jitter_bound, double* value, double* stats, double* gradient);
+
+/* ---- vessel splining --------------------------------------------------------------- */
+/* The per-slice sums behind com_from_image_list (imaging/utils/vessel.py:33-167) and get_com (label/utils.py:61-84), for
+ * every atlas's propagated label in one pass.  masks: HOST array of nmasks (1 ... 64) device pointers to uint8 volumes of
+ * `size` (x, y, z).  axis: the scan axis, 0 (x, sagittal, vessel.py:46-105) or 2 (z, axial, :107-167); anything else is
+ * PP_ERR_ARG (the reference's "y" falls through and crashes).  out (DEVICE, int64 [nmasks][size[axis]][4]) =
+ * {sum v, sum a v, sum b v, count(v != 0)} of each slice, v the voxel's own value (the reference weights by value: a 0 / 255
+ * mask weighs 255) and a, b the two in-slice array indices in the reference's order: z-scan row (image y) then column
+ * (image x), vessel.py:116-122; x-scan array z then array y, :55-61.  Integer arithmetic and integer atomics only: the
+ * table equals numpy's integer sums and a rerun gives the same bits.  The x-scan reads rows, never columns: the lanes of a
+ * wavefront lie along x, 16 bytes each where the masks are 16-byte aligned and size[0] % 16 == 0.  An axis longer than
+ * 65535 or 2^31 voxels or more: PP_ERR_SIZE.  No read-back, no synchronisation. */
+int pp_slice_moments_u8(pp_ctx* ctx, const uint8_t* const* masks, int nmasks, const int size[3], int axis, int64_t* out);
+/* The voxels within `radius` (mm) of a polyline: what vtkTubeFilter + vtkPolyDataToImageStencil make of the splined
+ * centreline at imaging/utils/vessel.py:170-296 -- a deviation, VTK is not used and parity with its voxelisation (50-sided
+ * tube, stencil tolerance 0.5) is UNPINNED.  points: HOST, npoints (>= 2) x 3 doubles in mm; the grid has identity
+ * direction (the reference forces it at vessel.py:406-407).  out[z][y][x] = 1 iff for some segment k the distance from the
+ * voxel centre origin + index * spacing to its closest point on the segment is <= radius, else 0; the ends are flat, as
+ * vtkTubeFilter does not cap: on the first segment only points whose unclamped projection parameter is >= 0 count, on the
+ * last only those with <= 1.  Segments of zero length are skipped (first and last then mean the first and last that remain);
+ * if none remains: PP_ERR_ARG.  Decided in fp64.  One workgroup per brick of 16 x 16 x 4 voxels culls the segment list
+ * against the brick's bounding sphere into LDS, in chunks, for any npoints.  Reruns are bit-identical.  Synchronises. */
+int pp_tube_mask_u8(pp_ctx* ctx, const double* points, int npoints, const int size[3], const double spacing[3],
+                    const double origin[3], double radius, uint8_t* out);
 
 #ifdef __cplusplus
 }

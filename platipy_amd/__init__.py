@@ -51,4 +51,5 @@ from . import registration  # noqa: E402,F401
 from . import label  # noqa: E402,F401
 from . import dose  # noqa: E402,F401
 from . import generation  # noqa: E402,F401
+from . import utils  # noqa: E402,F401
 from . import projects  # noqa: E402,F401

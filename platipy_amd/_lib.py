@@ -18,7 +18,7 @@ INTERP_NEAREST = 1
 INTERP_LINEAR = 2
 INTERP_BSPLINE = 3
 DEMONS_AUTO, DEMONS_STAGED, DEMONS_FUSED = 0, 1, 2
-ABI_VERSION = 3
+ABI_VERSION = 4
 HISTORY_CAPACITY = 4096     # PP_DEMONS_HISTORY_CAPACITY: iterations of one Execute whose metric / RMS change the device ring keeps
 
 
@@ -214,6 +214,9 @@ _SIGNATURES = {
     "pp_bspline_metric_f32": (C.c_int, [_P, C.c_int, _P, C.POINTER(Geom), _P, C.POINTER(Geom), C.POINTER(Geom), C.c_int, _P, _P, _P,
                                         C.POINTER(Geom), C.c_double, C.POINTER(C.c_double), C.POINTER(C.c_double),
                                         C.POINTER(C.c_double)]),
+    "pp_slice_moments_u8": (C.c_int, [_P, C.POINTER(_P), C.c_int, C.POINTER(C.c_int), C.c_int, _P]),
+    "pp_tube_mask_u8": (C.c_int, [_P, C.POINTER(C.c_double), C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_double), C.POINTER(C.c_double),
+                                  C.c_double, _P]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
@@ -625,6 +628,21 @@ class Context:
                                              int(t.size), counts.ctypes.data_as(C.POINTER(C.c_int64)))
         self._chk_value(rc, "pp_masked_count_ge_f32")
         return counts
+
+    # -- vessel splining ------------------------------------------------------------
+    def slice_moments(self, masks, size, axis, out):
+        """pp_slice_moments_u8: out (int64 device memory [len(masks)][size[axis]][4]) = {sum v, sum a v, sum b v, count} of every
+        slice along `axis` (0 = x, 2 = z) of the uint8 volumes `masks`; nothing is read back.  ValueError for another axis or
+        a mask count / size the library refuses."""
+        ptrs = (_P * max(len(masks), 1))(*[ptr(x) for x in masks])
+        self._chk_value(self.lib.pp_slice_moments_u8(self.h, ptrs, len(masks), _i3(size), int(axis), ptr(out)), "pp_slice_moments_u8")
+
+    def tube_mask(self, points, size, spacing, origin, radius, out):
+        """pp_tube_mask_u8: out (uint8 [Z][Y][X]) = 1 within `radius` mm of the polyline `points` ([n, 3] host doubles, mm), flat
+        ends.  ValueError for fewer than two points or a polyline of zero length."""
+        p = np.ascontiguousarray(points, dtype=np.float64).reshape(-1, 3)
+        self._chk_value(self.lib.pp_tube_mask_u8(self.h, p.ctypes.data_as(C.POINTER(C.c_double)), int(p.shape[0]), _i3(size), _d3(spacing),
+                                                 _d3(origin), float(radius), ptr(out)), "pp_tube_mask_u8")
 
     def label_contour(self, mask, size, out):
         self._chk(self.lib.pp_label_contour_u8(self.h, ptr(mask), _i3(size), ptr(out)), "pp_label_contour_u8")

@@ -1947,3 +1947,6 @@ int pp_linear_set_sample_jitter(pp_ctx* ctx, const float* jitter, size_t nsample
 
 // dose-volume histograms and dose metrics (imaging/dose/): pp_dose_histogram_f32, pp_masked_order_stats_f32, pp_masked_count_ge_f32
 #include "pp_dose.h"
+
+// vessel splining (imaging/utils/vessel.py): pp_slice_moments_u8, pp_tube_mask_u8
+#include "pp_vessel.h"

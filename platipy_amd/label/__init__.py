@@ -3,4 +3,4 @@ from .iar import distance_map, evaluate_distance_to_reference, label_contour, ru
 from . import comparison, utils  # noqa: F401
 from .utils import (  # noqa: F401
     binary_decode_image, binary_dilate, binary_encode_structure_list, binary_erode, binary_morphological_closing,
-    correct_volume_overlap, largest_component)
+    correct_volume_overlap, get_com, largest_component)

@@ -1,7 +1,8 @@
 """Drop-in for the pieces of platipy/imaging/label/utils.py the pipelines use after fusion:
 correct_volume_overlap (:23-58, element-wise tensor arithmetic on the GPU), plus the binary-mask SimpleITK calls
 the pipelines make inline -- BinaryDilate / BinaryErode / BinaryMorphologicalClosing with the ball kernel and
-"RelabelComponent(ConnectedComponent(x)) == 1" -- as HIP kernels (pp_morph.hip, pp_cc.hip)."""
+"RelabelComponent(ConnectedComponent(x)) == 1" -- as HIP kernels (pp_morph.hip, pp_cc.hip), and get_com (:61-84) from the
+per-slice moments kernel (pp_vessel.h)."""
 import numpy as np
 import torch
 
@@ -16,6 +17,9 @@ def _u8(image):
     return (t if t.dtype == torch.uint8 else (t != 0).to(torch.uint8)).contiguous()
 
 
+MAX_DILATE_RADIUS = 15   # voxels per axis: what the valve / conduction-node definitions may ask binary_dilate for
+
+
 def _radius3(image, radius):
     if not hasattr(radius, "__iter__"):
         radius = [radius] * 3
@@ -23,6 +27,14 @@ def _radius3(image, radius):
     if len(radius) != 3 or min(radius) < 0:
         raise ValueError(f"kernel radius must be three non-negative voxel counts, got {radius}")
     return radius
+
+
+def check_dilate_radius(radius, who):
+    """The geometric definitions dilate by a radius derived from mm and the spacing; above MAX_DILATE_RADIUS voxels on an axis
+    that is refused by name (two smaller balls are not one large ball, so nothing is composed)."""
+    if max(int(r) for r in radius) > MAX_DILATE_RADIUS:
+        raise ValueError(f"{who}: dilation radius {tuple(int(r) for r in radius)} voxels exceeds the limit of {MAX_DILATE_RADIUS} "
+                         "voxels per axis")
 
 
 def _morph(mask, radius, op):
@@ -100,3 +112,56 @@ def binary_decode_image(binary_encoded_img):
         if bool(s.any()):
             out.append(img.like(s.to(torch.uint8)))
     return out
+
+
+def _weights_u8(image, who):
+    """The label as the uint8 volume the moments kernel reads: its own values (the reference weights by value)."""
+    t = image.tensor
+    if t.dtype == torch.uint8:
+        return t.contiguous()
+    if t.dtype == torch.bool:
+        return t.to(torch.uint8).contiguous()
+    if t.dtype.is_floating_point or int(t.min()) < 0 or int(t.max()) > 255:
+        raise TypeError(f"{who}: the label must hold integers 0 ... 255 (uint8), got {t.dtype}")
+    return t.to(torch.uint8).contiguous()
+
+
+def slice_moments(labels, scan_direction="z"):
+    """int64 numpy array [len(labels), slices, 4] = {sum v, sum a v, sum b v, count(v != 0)} of every slice along
+    `scan_direction` ("z": a = row (image y), b = column (image x); "x": a = array z, b = array y) of labels on one grid:
+    the integer sums behind com_from_image_list (utils/vessel.py:33-167), exactly numpy's (pp_slice_moments_u8).  The
+    reference's "y" falls through and crashes; here it is a ValueError."""
+    axis = {"x": 0, "z": 2}.get(str(scan_direction).lower())
+    if axis is None:
+        raise ValueError(f"scan direction must be 'x' or 'z', got {scan_direction!r}")
+    labels = [as_image(l) for l in labels]
+    if len(labels) == 0:
+        raise ValueError("slice_moments: no labels")
+    size = labels[0].GetSize()
+    if any(l.GetSize() != size for l in labels):
+        raise ValueError("slice_moments: the labels must share one grid")
+    masks = [_weights_u8(l, "slice_moments") for l in labels]
+    ctx = runtime.context(labels[0].device)
+    out = torch.empty((len(masks), size[axis], 4), dtype=torch.int64, device=labels[0].device)
+    for k in range(0, len(masks), 64):     # the kernel takes 64 masks per launch
+        ctx.slice_moments(masks[k:k + 64], size, axis, out[k:k + 64])
+    return out.cpu().numpy()
+
+
+def get_com(label, as_int=True, real_coords=False):
+    """Centre of mass of a label (label/utils.py:61-84): scipy.ndimage.center_of_mass of the array, (z, y, x), from the exact
+    integer moments in fp64; as_int truncates each component, real_coords returns the physical point (x, y, z) instead.
+    An empty label gives NaN (int() of it raises, as in the reference)."""
+    label = as_image(label)
+    m = slice_moments([label], "z")[0]
+    total = float(m[:, 0].sum())
+    with np.errstate(divide="ignore", invalid="ignore"):
+        com = [np.float64(float((np.arange(m.shape[0], dtype=np.int64) * m[:, 0]).sum())) / total,
+               np.float64(float(m[:, 1].sum())) / total, np.float64(float(m[:, 2].sum())) / total]
+    if real_coords:
+        d = np.asarray(label.direction, dtype=np.float64).reshape(3, 3)
+        p = np.asarray(label.origin, dtype=np.float64) + d @ (np.asarray(label.spacing, dtype=np.float64) * np.array(com[::-1]))
+        return tuple(float(v) for v in p)
+    if as_int:
+        return [int(i) for i in com]
+    return tuple(float(c) for c in com)

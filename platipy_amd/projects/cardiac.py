@@ -6,9 +6,15 @@ What is built is the registration / label-fusion path of that function -- atlas 
 structure-guided demons on distance-map images of the guide structure, intensity demons, iterative atlas
 removal, weighted label fusion, paste-back and the connected-component / closing / overlap post-processing.
 
-Out of scope (not on the registration / fusion hot path) and refused loudly rather than
-silently skipped: vessel splining (cardiac/run.py:896-905, label/utils + vessel.py), the geometric valve and
-conduction-node definitions (:1046-1111), and the nnU-Net front end of run_hybrid_segmentation (:430-504).
+Vessel splining (cardiac/run.py:896-905, :1008-1042 -> utils/vessel.py) and the geometric valve and conduction-node
+definitions (:1046-1111 -> utils/valve.py, utils/conduction.py) are built too, but opt-in: with `geometry_stages=True` the
+reference's default settings run end to end and the results carry its ten further keys (four splined coronary vessels,
+four Valve_*, two CN_*).  Without the keyword the function behaves as before and refuses settings that ask for those stages
+loudly rather than skipping them silently.  The tube around the splined centreline is voxelised by a HIP kernel, not by
+VTK: parity with VTK's voxelisation is unpinned, and the spline's end conditions are vtkParametricSpline's defaults as
+recalled from upstream, unverified (utils/vessel.py).
+
+Out of scope: the nnU-Net front end of run_hybrid_segmentation (:430-504).
 Settings keep the reference's schema; CARDIAC_SETTINGS_DEFAULTS carries the reference's values.
 """
 import copy
@@ -128,7 +134,7 @@ CARDIAC_SETTINGS_DEFAULTS = {   # cardiac/run.py:75-270
 
 
 def run_cardiac_segmentation(img, guide_structure=None, settings=CARDIAC_SETTINGS_DEFAULTS, atlases=None, streams_per_gpu=1,
-                             return_atlas_set=False):
+                             return_atlas_set=False, geometry_stages=False, fusion_collective="all_reduce"):
     """Runs the atlas-based cardiac segmentation (reference cardiac/run.py:507-1147).
 
     img: target Image; guide_structure: optional binary Image on img's grid (e.g. a whole-heart mask) that
@@ -136,9 +142,21 @@ def run_cardiac_segmentation(img, guide_structure=None, settings=CARDIAC_SETTING
     nested dict.  `atlases` / `streams_per_gpu` as in multiatlas.run_segmentation (atlases are read from
     atlas_settings["atlas_path"] when not given).  Returns (results, results_prob), with return_atlas_set also the per-atlas
     propagated images / labels / weight maps (what the reference keeps in its atlas_set dictionary).
+
+    geometry_stages=True runs vessel splining (after atlas removal, on the kept atlases) and, on the pasted results and before
+    post-processing, the geometric valve and conduction-node definitions, as the settings ask for them; with the default
+    False such settings are refused.  With more than one rank these stages need fusion_collective="all_reduce".
     """
     settings = copy.deepcopy(settings)
     vessels = settings.get("vessel_spline_settings", {}).get("vessel_name_list", [])
+    if geometry_stages:
+        out = atlas_pipeline(as_image(img), settings, guide_structure, atlases, streams_per_gpu, cardiac=True,
+                             fusion_collective=fusion_collective, geometry_stages=True)
+        run_cardiac_segmentation.last_iar_removed = out["iar_removed"]
+        run_cardiac_segmentation.last_vessel_centrelines = out["vessel_centrelines"]      # {vessel: samples [10 N + 1, 3], mm}
+        if return_atlas_set:
+            return out["results"], out["results_prob"], out["atlas_set"]
+        return out["results"], out["results_prob"]
     if len(vessels) > 0:
         raise NotImplementedError(
             "run_cardiac_segmentation: vessel splining (vessel_spline_settings['vessel_name_list']) is outside this build's "
@@ -147,7 +165,7 @@ def run_cardiac_segmentation(img, guide_structure=None, settings=CARDIAC_SETTING
         raise NotImplementedError(
             "run_cardiac_segmentation: geometric valve / conduction-node definitions are outside this build's scope; set "
             "geometric_segmentation_settings['run_geometric_algorithms'] = False")
-    out = atlas_pipeline(as_image(img), settings, guide_structure, atlases, streams_per_gpu, cardiac=True)
+    out = atlas_pipeline(as_image(img), settings, guide_structure, atlases, streams_per_gpu, cardiac=True, fusion_collective=fusion_collective)
     run_cardiac_segmentation.last_iar_removed = out["iar_removed"]
     if return_atlas_set:
         return out["results"], out["results_prob"], out["atlas_set"]

@@ -22,6 +22,7 @@ import logging
 import os
 from concurrent.futures import ThreadPoolExecutor
 
+import numpy as np
 import torch
 
 from .. import runtime
@@ -166,6 +167,84 @@ class _Dist:
         return out
 
 
+def _spline_vessels(dd, img_crop, atlas_set, my_ids, kept_ids, vessel_names, vessel_set, device, centrelines):
+    """utils/vessel.py::vessel_spline_generation across ranks: every rank computes the per-slice moments of ITS atlases'
+    propagated vessel labels (pp_slice_moments_u8); the small int64 tables are all-gathered and placed in the order of the
+    kept atlases; every rank then runs the same fp64 host arithmetic on the same integers, so the centreline -- and the tube
+    voxelised from it -- is bit-identical for any world size.  The grid is the cropped target's with the direction forced to
+    identity while the vessel is drawn (the reference's V6).  `centrelines` receives {vessel: samples [10 N + 1, 3]}."""
+    from ..label.utils import slice_moments
+    from ..utils.vessel import com_from_moments, simpleitk_image_from_vtk_tube, tube_from_com_list
+
+    out = {}
+    flat = img_crop.like(img_crop.tensor)
+    flat.SetDirection((1, 0, 0, 0, 1, 0, 0, 0, 1))
+    size = img_crop.GetSize()
+    host = torch.device("cpu") if (dd.dist is not None and dd.dist.get_backend() != "nccl") else device
+    for s in vessel_names:
+        scan = str(vessel_set["scan_direction_dict"][s]).lower()
+        if scan not in ("x", "z"):
+            raise ValueError(f"scan direction must be 'x' or 'z', got {scan!r}")
+        nslices = size[0] if scan == "x" else size[2]
+        mine = [a for a in kept_ids if a in my_ids and s in atlas_set[a]["DIR"]]
+        table = torch.zeros((len(kept_ids), nslices * 4 + 1), dtype=torch.int64)
+        if mine:
+            m = slice_moments([atlas_set[a]["DIR"][s] for a in mine], scan)
+            for row, a in zip(m, mine):
+                k = kept_ids.index(a)
+                table[k, :-1] = torch.from_numpy(np.ascontiguousarray(row.reshape(-1)))
+                table[k, -1] = 1      # this atlas carries the vessel
+        for a in kept_ids:
+            if a in my_ids and s not in atlas_set[a]["DIR"]:
+                logger.warning("No match for ID=%s, label=%s, vessel=%s", a, "DIR", s)
+        gathered = torch.stack([t.cpu() for t in dd.all_gather(table.to(host))]).sum(dim=0)      # (rows are disjoint between ranks)
+        present = gathered[:, -1] != 0
+        if not bool(present.any()):
+            logger.warning("No structures found for vessel with name %s!", s)
+            continue
+        moments = gathered[present][:, :-1].reshape(-1, nslices, 4).numpy()
+        points = com_from_moments(moments, flat, vessel_set["stop_condition_type_dict"][s], vessel_set["stop_condition_value_dict"][s], scan)
+        tube = tube_from_com_list(points, radius=vessel_set["vessel_radius_mm_dict"][s])
+        vessel = simpleitk_image_from_vtk_tube(tube, flat)
+        vessel.SetDirection(img_crop.GetDirection())
+        out[s] = vessel
+        centrelines[s] = np.asarray(tube).copy()
+    return out
+
+
+def geometric_definitions(results, geometric_segmentation_settings):
+    """Step 7 of the cardiac pipeline (cardiac/run.py:1047-1108): the four valves and the two conduction-system nodes from the
+    fused structures in `results` -> {name: binary Image}."""
+    from ..utils.conduction import geometric_atrioventricularnode, geometric_sinoatrialnode
+    from ..utils.valve import generate_valve_from_great_vessel, generate_valve_using_cylinder
+
+    logger.info("Computing geometric definitions for valves and conduction system.")
+    names = geometric_segmentation_settings["atlas_structure_names"]
+    valves = geometric_segmentation_settings["valve_definitions"]
+    nodes = geometric_segmentation_settings["conduction_system_definitions"]
+    out = {}
+    out["Valve_Mitral"] = generate_valve_using_cylinder(
+        label_atrium=results[names["atlas_left_atrium"]], label_ventricle=results[names["atlas_left_ventricle"]],
+        radius_mm=valves["mitral_valve_radius_mm"], height_mm=valves["mitral_valve_thickness_mm"])
+    out["Valve_Tricuspid"] = generate_valve_using_cylinder(
+        label_atrium=results[names["atlas_right_atrium"]], label_ventricle=results[names["atlas_right_ventricle"]],
+        radius_mm=valves["tricuspid_valve_radius_mm"], height_mm=valves["tricuspid_valve_thickness_mm"])
+    out["Valve_Aortic"] = generate_valve_from_great_vessel(
+        label_great_vessel=results[names["atlas_ascending_aorta"]], label_ventricle=results[names["atlas_left_ventricle"]],
+        valve_thickness_mm=valves["aortic_valve_thickness_mm"])
+    out["Valve_Pulmonic"] = generate_valve_from_great_vessel(
+        label_great_vessel=results[names["atlas_pulmonary_artery"]], label_ventricle=results[names["atlas_right_ventricle"]],
+        valve_thickness_mm=valves["pulmonic_valve_thickness_mm"])
+    out["CN_Sinoatrial"] = geometric_sinoatrialnode(
+        label_svc=results[names["atlas_superior_vena_cava"]], label_ra=results[names["atlas_right_atrium"]],
+        label_wholeheart=results[names["atlas_whole_heart"]], radius_mm=nodes["sinoatrial_node_radius_mm"])
+    out["CN_Atrioventricular"] = geometric_atrioventricularnode(
+        label_la=results[names["atlas_left_atrium"]], label_lv=results[names["atlas_left_ventricle"]],
+        label_ra=results[names["atlas_right_atrium"]], label_rv=results[names["atlas_right_ventricle"]],
+        radius_mm=nodes["atrioventricular_node_radius_mm"])
+    return out
+
+
 _STREAM_POOL = {}   # device index -> long-lived worker streams (each owns one pp_ctx + workspace, see runtime.context)
 
 
@@ -282,18 +361,28 @@ def run_segmentation(img, settings=MUTLIATLAS_SETTINGS_DEFAULTS, atlases=None, s
     return out["results"], out["results_prob"]
 
 
-def atlas_pipeline(img, settings, guide_structure=None, atlases=None, streams_per_gpu=1, cardiac=False, fusion_collective="all_reduce"):
+def atlas_pipeline(img, settings, guide_structure=None, atlases=None, streams_per_gpu=1, cardiac=False, fusion_collective="all_reduce",
+                   geometry_stages=False):
     """The skeleton shared by run_segmentation (multiatlas/run.py:106-441) and run_cardiac_segmentation
     (cardiac/run.py:507-1147): read atlases -> crop the target -> per atlas [linear -> (structure-guided demons)
     -> demons -> propagate] -> (iterative atlas removal) -> weight maps -> fuse -> threshold -> paste back ->
     post-process.  `cardiac` selects the cardiac pipeline's result conventions (only structures with an
-    optimal_threshold are voted, the guide structure is handed back, return_as_cropped).
+    optimal_threshold are voted, the guide structure is handed back, return_as_cropped).  `geometry_stages` (cardiac only)
+    adds the reference's vessel splining after atlas removal (cardiac/run.py:897-905, :1008-1042) and its geometric valve /
+    conduction-node definitions on the pasted results BEFORE post-processing (:1047-1108).
     Returns a dict: results, results_prob, atlas_set, iar_removed, img_crop."""
     if fusion_collective not in ("all_reduce", "reduce"):
         raise ValueError("fusion_collective must be 'all_reduce' or 'reduce'")
     img = as_image(img)
     settings = copy.deepcopy(settings)
     dd = _Dist()
+    vessel_set = dict(settings.get("vessel_spline_settings") or {}) if (cardiac and geometry_stages) else {}
+    vessel_names = vessel_set.get("vessel_name_list", [])
+    vessel_names = [vessel_names] if isinstance(vessel_names, str) else list(vessel_names)
+    geom_set = dict(settings.get("geometric_segmentation_settings") or {}) if (cardiac and geometry_stages) else {}
+    run_geometric = bool(geom_set.get("run_geometric_algorithms", False))
+    if (vessel_names or run_geometric) and fusion_collective == "reduce" and dd.world > 1:
+        raise NotImplementedError("geometry_stages needs every rank's results: use fusion_collective='all_reduce'")
     device = img.device
     a_set = settings["atlas_settings"]
     atlas_id_list = list(a_set["atlas_id_list"])
@@ -437,6 +526,14 @@ def atlas_pipeline(img, settings, guide_structure=None, atlases=None, streams_pe
     else:
         logger.info("IAR: No reference structure, skipping iterative atlas removal.")
 
+    # ---- vessel splining on the kept atlases (cardiac/run.py:897-905 -> utils/vessel.py) ----
+    kept_ids = [i for i in atlas_id_list if i not in removed]
+    segmented_vessel_dict, vessel_centrelines = {}, {}
+    if vessel_names:
+        dd.label = "vessel_moments"
+        segmented_vessel_dict = _spline_vessels(dd, img_crop, atlas_set, my_ids, kept_ids, vessel_names, vessel_set, device, vessel_centrelines)
+        dd.label = "other"
+
     # ---- step 5: weight maps + label fusion, the one cross-atlas exchange (fusion.py:263-288) ----
     vote_type = settings["label_fusion_settings"]["vote_type"]
     vote_params = settings["label_fusion_settings"]["vote_params"]
@@ -515,6 +612,30 @@ def atlas_pipeline(img, settings, guide_structure=None, atlases=None, streams_pe
             results[guide_structure_name] = g
             results_prob[guide_structure_name] = g
 
+    # ---- the splined vessels, and each atlas's propagated vessel in bit k + 1 of results_prob (cardiac :1008-1042) ----
+    for s in vessel_names:
+        if s not in segmented_vessel_dict:
+            continue
+        enc = torch.zeros(img_crop.shape, dtype=torch.int64, device=device)
+        if len(kept_ids) > 32:
+            raise ValueError("You can only encode a maximum of 32 structures with this method!")
+        for pos, a in enumerate(kept_ids):      # every rank encodes its own atlases; the bit sets are disjoint (see above)
+            if a in my_ids and s in atlas_set[a]["DIR"]:
+                enc |= (atlas_set[a]["DIR"][s].tensor != 0).to(torch.int64) << (pos + 1)
+        dd.label = "vessel_allreduce"
+        dd.all_reduce_sum(enc)
+        dd.label = "other"
+        vessel = segmented_vessel_dict[s]
+        if as_cropped:
+            results[s], results_prob[s] = vessel, img_crop.like(enc)
+        else:
+            results[s] = paste(template_binary, vessel, crop_box_index)
+            results_prob[s] = paste(img.like(torch.zeros(img.shape, dtype=torch.int64, device=device)), img_crop.like(enc), crop_box_index)
+
+    # ---- step 7: geometric definitions of the valves and the conduction-system nodes (cardiac :1047-1108) ----
+    if run_geometric:
+        results.update(geometric_definitions(results, geom_set))
+
     # ---- step 8: post-processing (:409-437; cardiac :1113-1141), on the device ----
     pp = settings["postprocessing_settings"]
     if pp["run_postprocessing"]:
@@ -534,5 +655,5 @@ def atlas_pipeline(img, settings, guide_structure=None, atlases=None, streams_pe
     if as_cropped:
         results["CROP_IMAGE"] = img_crop
     return {"results": results, "results_prob": results_prob, "atlas_set": atlas_set, "iar_removed": removed, "img_crop": img_crop,
-            "crop_box": (list(crop_box_size), list(crop_box_index)),
+            "crop_box": (list(crop_box_size), list(crop_box_index)), "vessel_centrelines": vessel_centrelines,
             "fusion_payload_bytes": fusion_payload_bytes, "exchange_ms": dd.timings_ms(), "world_size": dd.world}

@@ -184,6 +184,22 @@ class VersorRigid3DTransform(_Parametrised):
 
     update = staticmethod(_versor_update)
 
+    def SetRotation(self, axis, angle):
+        """sitk.VersorRigid3DTransform.SetRotation(axis, angle) (itk::Versor::Set(axis, angle)): the versor
+        axis / |axis| * sin(angle / 2), w = cos(angle / 2); the translation is kept.  Only the vector part is stored and w is
+        taken as +sqrt(1 - |v|^2), so for cos(angle / 2) < 0 the vector part is negated (the same rotation).  A zero-length
+        axis raises ValueError (ITK throws there)."""
+        axis = np.asarray(axis, dtype=np.float64).reshape(3)
+        norm = float(np.sqrt(axis[0] * axis[0] + axis[1] * axis[1] + axis[2] * axis[2]))
+        if not norm > 0.0 or not np.isfinite(norm):
+            raise ValueError("SetRotation: the rotation axis must have a finite, non-zero length")
+        v = axis * (np.sin(float(angle) / 2.0) / norm)
+        if np.cos(float(angle) / 2.0) < 0.0:
+            v = -v
+        p = self._params.copy()
+        p[:3] = v
+        self.SetParameters(p)
+
 
 class Similarity3DTransform(_Parametrised):
     """parameters: versor (x, y, z), translation (3), isotropic scale"""
