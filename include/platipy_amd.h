@@ -149,7 +149,8 @@ int pp_recursive_gaussian_f32(pp_ctx* ctx, const float* in, float* out, const pp
 
 /* ONE directional pass of itk::RecursiveGaussianImageFilter over a scalar volume (in != out): order 0 the Gaussian, order 1 its
  * first derivative along `axis` per VOXEL (a unit ramp answers 1; times sigma when normalize_across_scale, as ITK's
- * NormalizeAcrossScale).  The building block of itk::GradientRecursiveGaussianImageFilter -- derivative along one axis, then
+ * NormalizeAcrossScale).  The spacing of `axis` may be negative: the filter uses its magnitude and the first-order response takes
+ * its sign, as ITK's does (every other spacing must be positive).  The building block of itk::GradientRecursiveGaussianImageFilter -- derivative along one axis, then
  * Gaussians along the others -- which itk::ImageToImageMetricv4 runs over the moving image (sigma = its largest spacing) inside
  * registration.Execute (registration/linear.py:238) as the metric's default gradient source; the host chains the passes
  * (platipy_amd/registration/linear.py, itk_sampling=True). */

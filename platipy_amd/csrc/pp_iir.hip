@@ -599,7 +599,14 @@ int pp_recursive_gaussian_pass_f32(pp_ctx* ctx, const float* in, float* out, con
   pp_device_guard dev_guard_(ctx);
   PP_REQUIRE(ctx, in && out && in != out, "pp_recursive_gaussian_pass_f32: two distinct volumes");
   PP_REQUIRE(ctx, axis >= 0 && axis < 3 && (order == 0 || order == 1), "pp_recursive_gaussian_pass_f32: axis 0..2, order 0 or 1");
-  int rc = pp_geom_check(ctx, g, "grid");
+  // the pass axis may carry a NEGATIVE spacing (ITK filters on its magnitude and gives the first-order response its sign):
+  // the grid is checked with the magnitude there, every other rule of pp_geom_check holds as it stands
+  pp_geom ga;
+  if (g) {
+    ga = *g;
+    ga.spacing[axis] = std::fabs(ga.spacing[axis]);
+  }
+  int rc = pp_geom_check(ctx, g ? &ga : nullptr, "grid");
   if (rc) return rc;
   const pp_dims d{g->size[0], g->size[1], g->size[2]};
   // first order: the response to a unit ramp per voxel is 1; ITK multiplies it by sigma (physical) when NormalizeAcrossScale
