@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define PP_ABI_VERSION 4
+#define PP_ABI_VERSION 5
 
 typedef enum {
   PP_OK = 0,
@@ -42,7 +42,8 @@ typedef enum {
   PP_ERR_UNSUPPORTED = -4, /* valid request this build does not implement         */
   PP_ERR_SIZE = -5,        /* volume too small / too large for the operation      */
   PP_ERR_NO_OVERLAP = -6,  /* linear registration: no valid sample point at start */
-  PP_ERR_DIRECTION = -7    /* B-spline metric: lattice / virtual / fixed direction cosines differ */
+  PP_ERR_DIRECTION = -7,   /* B-spline metric: lattice / virtual / fixed direction cosines differ */
+  PP_ERR_INVALID = -8      /* a value that points outside the data it refers to (a seed outside the buffer) */
 } pp_status;
 
 enum { PP_INTERP_NEAREST = 1, PP_INTERP_LINEAR = 2, PP_INTERP_BSPLINE = 3 }; /* = sitk.sitkNearestNeighbor / sitkLinear / sitkBSpline */
@@ -590,6 +591,36 @@ int pp_slice_moments_u8(pp_ctx* ctx, const uint8_t* const* masks, int nmasks, co
  * against the brick's bounding sphere into LDS, in chunks, for any npoints.  Reruns are bit-identical.  Synchronises. */
 int pp_tube_mask_u8(pp_ctx* ctx, const double* points, int npoints, const int size[3], const double spacing[3],
                     const double origin[3], double radius, uint8_t* out);
+
+/* ---- region primitives (airway and lung segmentation) ------------------------------- */
+/* sitk.ConnectedComponent(mask) with face connectivity (imaging/utils/lung.py:41-42, projects/bronchus/bronchus.py:214 and
+ * :331-333): labels (DEVICE, int32, `size` voxels) = 0 on background (mask == 0), and 1 ... N on the components, numbered in
+ * raster order of their first voxel -- the order ITK numbers them in [ITK-upstream, unverified here; SimpleITK is absent].
+ * The labelling is the union-find of pp_fillhole_largest_component_u8 (a component's root is its first voxel); the roots
+ * are then ranked by a reduce-then-scan over the volume in separate launches, no block waits for another.  count (HOST, may
+ * be NULL) receives N (GetObjectCount); non-NULL synchronises.  2^31 voxels or more: PP_ERR_SIZE.  Reruns are
+ * bit-identical. */
+int pp_connected_components_u8(pp_ctx* ctx, const uint8_t* mask, const int size[3], int32_t* labels, int* count);
+/* The sums sitk.LabelShapeStatisticsImageFilter derives size, centroid and principal moments from (lung.py:46-56,
+ * bronchus.py:221-229, :336-339), for every label in one pass.  labels: DEVICE int32 volume (4-byte aligned); out: DEVICE
+ * int64 [nlabels][10] = {count, sum x, sum y, sum z, sum xx, sum yy, sum zz, sum xy, sum xz, sum yz} over the voxel indices of
+ * label l in row l - 1.  Label 0, negative labels and labels above nlabels are ignored; a label that does not occur gives
+ * zeros.  Exact integer sums (modulo 2^64) by 64-bit integer atomics, equal labels combined inside the block first; reruns
+ * are bit-identical.  2^31 voxels or more: PP_ERR_SIZE.  No read-back, no synchronisation. */
+int pp_label_moments_i32(pp_ctx* ctx, const int32_t* labels, const int size[3], int nlabels, int64_t* out);
+/* sitk.ConnectedThreshold(image, seedList, lower, upper) (bronchus.py:259-262): out (DEVICE uint8) = 1 on every voxel that
+ * is face-connected to a seed through voxels with lower <= v <= upper -- both ends included, compared in double, a NaN
+ * never joins -- and 0 elsewhere.  seeds: HOST, nseeds x 3 indices (x, y, z); a seed whose own voxel is outside the interval
+ * contributes nothing, a seed outside the buffer is PP_ERR_INVALID (ITK raises).  Threshold, the labelling of
+ * pp_connected_components_u8, then the components of the seeds' roots.  voxels (HOST, may be NULL): the size of the region.
+ * 2^31 voxels or more: PP_ERR_SIZE.  Reruns are bit-identical.  Synchronises. */
+int pp_connected_threshold_f32(pp_ctx* ctx, const float* image, const int size[3], double lower, double upper, const int* seeds,
+                               int nseeds, uint8_t* out, int64_t* voxels);
+/* sitk.Median(mask, radius) on a 0 / non-zero mask (bronchus.py:194-196): out = 1 iff more than half of the
+ * (2 rx + 1)(2 ry + 1)(2 rz + 1) window is non-zero, the window clamped to the volume (edge replication, ITK's zero-flux
+ * Neumann condition).  radius (x, y, z) in 0 ... 2, anything else PP_ERR_ARG; `out` must not alias `in`.  From an LDS tile
+ * with halo. */
+int pp_binary_median_u8(pp_ctx* ctx, const uint8_t* in, const int size[3], const int radius[3], uint8_t* out);
 
 #ifdef __cplusplus
 }

@@ -18,7 +18,7 @@ INTERP_NEAREST = 1
 INTERP_LINEAR = 2
 INTERP_BSPLINE = 3
 DEMONS_AUTO, DEMONS_STAGED, DEMONS_FUSED = 0, 1, 2
-ABI_VERSION = 4
+ABI_VERSION = 5
 HISTORY_CAPACITY = 4096     # PP_DEMONS_HISTORY_CAPACITY: iterations of one Execute whose metric / RMS change the device ring keeps
 
 
@@ -54,6 +54,7 @@ ERR_UNSUPPORTED = -4
 RESAMPLE_SET_MAX_LABELS = 16    # PP_RESAMPLE_SET_MAX_LABELS
 ERR_NO_OVERLAP = -6
 ERR_DIRECTION = -7
+ERR_INVALID = -8        # PP_ERR_INVALID: a seed outside the buffer
 BSPLINE_MEAN_SQUARES, BSPLINE_CORRELATION = 0, 1
 MODEL_TRANSLATION, MODEL_VERSOR_RIGID, MODEL_SIMILARITY, MODEL_SCALE, MODEL_AFFINE, MODEL_EULER, MODEL_SCALE_VERSOR, MODEL_SCALE_SKEW_VERSOR = range(8)
 OPT_GD, OPT_GD_LINE_SEARCH = 0, 1
@@ -217,6 +218,11 @@ _SIGNATURES = {
     "pp_slice_moments_u8": (C.c_int, [_P, C.POINTER(_P), C.c_int, C.POINTER(C.c_int), C.c_int, _P]),
     "pp_tube_mask_u8": (C.c_int, [_P, C.POINTER(C.c_double), C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_double), C.POINTER(C.c_double),
                                   C.c_double, _P]),
+    "pp_connected_components_u8": (C.c_int, [_P, _P, C.POINTER(C.c_int), _P, C.POINTER(C.c_int)]),
+    "pp_label_moments_i32": (C.c_int, [_P, _P, C.POINTER(C.c_int), C.c_int, _P]),
+    "pp_connected_threshold_f32": (C.c_int, [_P, _P, C.POINTER(C.c_int), C.c_double, C.c_double, C.POINTER(C.c_int), C.c_int, _P,
+                                             C.POINTER(C.c_int64)]),
+    "pp_binary_median_u8": (C.c_int, [_P, _P, C.POINTER(C.c_int), C.POINTER(C.c_int), _P]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
@@ -643,6 +649,40 @@ class Context:
         p = np.ascontiguousarray(points, dtype=np.float64).reshape(-1, 3)
         self._chk_value(self.lib.pp_tube_mask_u8(self.h, p.ctypes.data_as(C.POINTER(C.c_double)), int(p.shape[0]), _i3(size), _d3(spacing),
                                                  _d3(origin), float(radius), ptr(out)), "pp_tube_mask_u8")
+
+    # -- region primitives ------------------------------------------------------------
+    def connected_components(self, mask, size, labels, want_count=True):
+        """pp_connected_components_u8: labels (int32) = sitk.ConnectedComponent of the uint8 mask, face connectivity, numbered
+        in raster order of first voxels -> the number of components (synchronises), or None without want_count."""
+        n = C.c_int(0)
+        self._chk_value(self.lib.pp_connected_components_u8(self.h, ptr(mask), _i3(size), ptr(labels), C.byref(n) if want_count else None),
+                        "pp_connected_components_u8")
+        return n.value if want_count else None
+
+    def label_moments(self, labels, size, nlabels, out):
+        """pp_label_moments_i32: out (int64 device memory [nlabels][10]) = {count, sum x, y, z, xx, yy, zz, xy, xz, yz} over the
+        voxel indices of labels 1 ... nlabels of the int32 volume; nothing is read back."""
+        self._chk_value(self.lib.pp_label_moments_i32(self.h, ptr(labels), _i3(size), int(nlabels), ptr(out)), "pp_label_moments_i32")
+
+    def connected_threshold(self, image, size, lower, upper, seeds, out):
+        """pp_connected_threshold_f32: out (uint8) = sitk.ConnectedThreshold of the float32 volume from `seeds` ([n, 3] indices
+        x, y, z) -> voxels in the region (synchronises).  IndexError for a seed outside the buffer."""
+        s = np.ascontiguousarray(seeds, dtype=np.int32).reshape(-1, 3)
+        vox = C.c_int64(0)
+        rc = self.lib.pp_connected_threshold_f32(self.h, ptr(image), _i3(size), float(lower), float(upper),
+                                                 s.ctypes.data_as(C.POINTER(C.c_int)), int(s.shape[0]), ptr(out), C.byref(vox))
+        if rc == ERR_INVALID:
+            msg = self.lib.pp_last_error(self.h)
+            err = IndexError(msg.decode(errors="replace") if msg else "pp_connected_threshold_f32: seed outside the buffer")
+            err.code = rc
+            raise err
+        self._chk_value(rc, "pp_connected_threshold_f32")
+        return vox.value
+
+    def binary_median(self, mask, size, radius, out):
+        """pp_binary_median_u8: out = 1 where more than half of the (2 r + 1)^3 window (edge-replicated) of the uint8 mask is
+        non-zero; radius (x, y, z) in 0 ... 2."""
+        self._chk_value(self.lib.pp_binary_median_u8(self.h, ptr(mask), _i3(size), _i3(radius), ptr(out)), "pp_binary_median_u8")
 
     def label_contour(self, mask, size, out):
         self._chk(self.lib.pp_label_contour_u8(self.h, ptr(mask), _i3(size), ptr(out)), "pp_label_contour_u8")

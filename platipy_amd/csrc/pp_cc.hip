@@ -349,3 +349,6 @@ extern "C" int pp_fillhole_largest_component_u8(pp_ctx* ctx, const uint8_t* in, 
   }
   return PP_OK;
 }
+
+// connected-component numbering, per-label moments, seeded region growing, binary median: built on cc_label above
+#include "pp_region.h"

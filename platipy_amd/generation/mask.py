@@ -1,7 +1,7 @@
 """Drop-in for platipy/imaging/generation/mask.py: extend_mask (:107-159), used by the structure-guided cardiac
 pipeline (projects/cardiac/run.py:741-746, 826-831) -- a handful of slice copies on the device tensor -- and get_bone_mask
 (:21-47), which generate_random_augmentation needs.  get_external_mask (per-slice convex hulls from scikit-image) has no
-counterpart here."""
+counterpart here; the external mask of imaging/utils/lung.py (the closed outside-air component) is utils/lung.py's."""
 import numpy as np
 import torch
 

@@ -12,3 +12,4 @@ from .utils import (  # noqa: F401
     smooth_and_resample,
     transform_to_displacement_field,
 )
+from ..label.region import connected_threshold  # noqa: E402,F401  (sitk.ConnectedThreshold: a region-growing segmentation filter)

@@ -1,2 +1,2 @@
-"""Drop-in for platipy/imaging/utils: crop.py, geometry.py, vessel.py, valve.py, conduction.py."""
-from . import conduction, crop, geometry, valve, vessel  # noqa: F401
+"""Drop-in for platipy/imaging/utils: crop.py, geometry.py, vessel.py, valve.py, conduction.py, lung.py."""
+from . import conduction, crop, geometry, lung, valve, vessel  # noqa: F401
