@@ -622,6 +622,48 @@ int pp_connected_threshold_f32(pp_ctx* ctx, const float* image, const int size[3
  * with halo. */
 int pp_binary_median_u8(pp_ctx* ctx, const uint8_t* in, const int size[3], const int radius[3], uint8_t* out);
 
+/* ---- left-ventricle 17-segment model (imaging/utils/ventricle.py) -------------------- */
+/* The segment assignment of generate_left_ventricle_segments (ventricle.py:408-644: a Python loop over slices with 4 or 6
+ * `extract` calls each, :30-72) for every slice at once.  mask: DEVICE uint8 [Z][Y][X], non-zero = inside.  slices: HOST,
+ * one pp_polar_slice per z-slice; nrules == 0 skips the slice (its bits are written as 0, its counts stay 0).  rules: HOST,
+ * nrules_total pp_polar_rule; slice z uses rules[first_rule ... first_rule + nrules).  For every mask voxel (y, x) of a
+ * slice, in fp64, one rounding per operation, in this order:
+ *     dy = y - cy, dx = x - cx;  theta = -atan2(dy, dx) - theta0;  if (theta < 0) theta += 2 pi  (ONCE: the angle may stay
+ *     negative, and then matches no sector with angle_min >= 0, only a PP_POLAR_CW one);  r = sqrt(dy * dy + dx * dx)
+ * A rule matches when r >= radius_min and -- PP_POLAR_CW set -- theta <= angle_min || theta >= angle_max, otherwise
+ * theta >= angle_min && theta <= angle_max; both ends are inclusive, so a voxel on a boundary matches two rules.
+ * angle_min = -inf, angle_max = +inf is "the whole slice".  counts (DEVICE, int64 [Z][32]): the voxels of slice z that match
+ * a rule of label l, in [z][l - 1], before any suppression (a voxel counts once per label however many rules of that label
+ * it matches).  A (slice, label) pair with (double)count * area < min_area_mm2 is suppressed as a whole (ventricle.py:67-70;
+ * equality keeps it) unless a rule of that label on that slice carries PP_POLAR_ANY_AREA (the reference's segment 17 is
+ * never put to the area test, :325-327).  bits (DEVICE, uint32 [Z][Y][X]): bit l - 1 set for every surviving match, 0
+ * elsewhere; every voxel is written.  Two launches on the context's stream -- count, then write, which reads the counts
+ * on the device; integer atomics only, so a rerun gives the same bits.  Labels outside 1 ... 32, a rule range outside the
+ * table, unknown flags, NaN angles or areas, a centre that is not finite: PP_ERR_ARG before anything is written; an axis
+ * longer than 65535: PP_ERR_SIZE.  The fp64 atan2 is the device library's: a voxel within an ulp of a sector boundary may
+ * fall on either side of it compared with another libm.  Synchronises (the tables are host memory of the call). */
+enum { PP_POLAR_CW = 1, PP_POLAR_ANY_AREA = 2 };
+typedef struct pp_polar_slice {
+  double cy, cx;      /* the slice's centre: row (y), column (x) */
+  double theta0;      /* subtracted from every angle */
+  double radius_min;  /* voxels */
+  int first_rule, nrules;
+} pp_polar_slice;
+typedef struct pp_polar_rule {
+  int label;          /* 1 ... 32 */
+  int flags;          /* PP_POLAR_CW | PP_POLAR_ANY_AREA */
+  double angle_min, angle_max;
+} pp_polar_rule;
+int pp_polar_sectors_u8(pp_ctx* ctx, const uint8_t* mask, const int size[3], const pp_polar_slice* slices, const pp_polar_rule* rules,
+                        int nrules_total, double area, double min_area_mm2, uint32_t* bits, int64_t* counts);
+/* The way back into image space (ventricle.py:660-666, 17 sitk.Resample calls): nearest-neighbour resample of the uint32 bit
+ * image `in` on `gin` through the LINEAR transform q = A p + t (NULL: identity) onto `gout`, unpacked: out (DEVICE uint8
+ * [nbits][Z][Y][X] on gout) plane k = bit k of the picked voxel, 0 outside the buffer.  Coordinates, inside test and
+ * rounding are pp_resample_u8's nearest-neighbour path (the same device functions), so plane k equals pp_resample_u8 of
+ * bit k as a uint8 volume, default 0.  nbits in 1 ... 32.  One read of the source, nbits byte planes written. */
+int pp_resample_bits_u32(pp_ctx* ctx, const uint32_t* in, const pp_geom* gin, const pp_geom* gout, const double* affine_A,
+                         const double* affine_t, int nbits, uint8_t* out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -121,6 +121,12 @@ DOSE_MAX_LABELS, DOSE_MAX_BINS, ORDER_STATS_MAX_RANKS = 64, 1 << 20, 8
 DOSE_STATS_DTYPE = np.dtype([("count", "<i8"), ("mask_sum", "<i8"), ("dose_sum", "<f8"), ("dose_min", "<f4"), ("dose_max", "<f4")])
 
 
+POLAR_CW, POLAR_ANY_AREA = 1, 2      # PP_POLAR_CW, PP_POLAR_ANY_AREA
+# pp_polar_slice / pp_polar_rule as numpy records (host tables of pp_polar_sectors_u8)
+POLAR_SLICE_DTYPE = np.dtype([("cy", "<f8"), ("cx", "<f8"), ("theta0", "<f8"), ("radius_min", "<f8"), ("first_rule", "<i4"), ("nrules", "<i4")])
+POLAR_RULE_DTYPE = np.dtype([("label", "<i4"), ("flags", "<i4"), ("angle_min", "<f8"), ("angle_max", "<f8")])
+
+
 class PlatipyAmdError(RuntimeError):
     pass
 
@@ -223,6 +229,8 @@ _SIGNATURES = {
     "pp_connected_threshold_f32": (C.c_int, [_P, _P, C.POINTER(C.c_int), C.c_double, C.c_double, C.POINTER(C.c_int), C.c_int, _P,
                                              C.POINTER(C.c_int64)]),
     "pp_binary_median_u8": (C.c_int, [_P, _P, C.POINTER(C.c_int), C.POINTER(C.c_int), _P]),
+    "pp_polar_sectors_u8": (C.c_int, [_P, _P, C.POINTER(C.c_int), _P, _P, C.c_int, C.c_double, C.c_double, _P, _P]),
+    "pp_resample_bits_u32": (C.c_int, [_P, _P, C.POINTER(Geom), C.POINTER(Geom), C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_int, _P]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
@@ -683,6 +691,31 @@ class Context:
         """pp_binary_median_u8: out = 1 where more than half of the (2 r + 1)^3 window (edge-replicated) of the uint8 mask is
         non-zero; radius (x, y, z) in 0 ... 2."""
         self._chk_value(self.lib.pp_binary_median_u8(self.h, ptr(mask), _i3(size), _i3(radius), ptr(out)), "pp_binary_median_u8")
+
+    # -- left-ventricle segments ------------------------------------------------------
+    def polar_sectors(self, mask, size, slices, rules, area, min_area_mm2, bits, counts):
+        """pp_polar_sectors_u8: bits (uint32 [Z][Y][X]) and counts (int64 [Z][32], both device memory) from the uint8 `mask`.
+        slices: one (cy, cx, theta0, radius_min, first_rule, nrules) per z-slice (or a POLAR_SLICE_DTYPE array), nrules 0 =
+        skipped; rules: (label 1 ... 32, flags POLAR_CW | POLAR_ANY_AREA, angle_min, angle_max) (or a POLAR_RULE_DTYPE array).
+        ValueError for a table that does not have one entry per slice and for whatever the library refuses (a label outside
+        1 ... 32, a rule range outside the table, a NULL buffer, an empty volume); the outputs are then untouched."""
+        st = slices if isinstance(slices, np.ndarray) and slices.dtype == POLAR_SLICE_DTYPE else np.array([tuple(v) for v in slices], dtype=POLAR_SLICE_DTYPE)
+        rt = rules if isinstance(rules, np.ndarray) and rules.dtype == POLAR_RULE_DTYPE else np.array([tuple(v) for v in rules], dtype=POLAR_RULE_DTYPE)
+        st, rt = np.ascontiguousarray(st).reshape(-1), np.ascontiguousarray(rt).reshape(-1)
+        if len(size) != 3 or st.size != max(int(size[2]), 0):
+            raise ValueError(f"polar_sectors: {st.size} slice entries for a volume of size {tuple(size)}")
+        self._chk_value(self.lib.pp_polar_sectors_u8(self.h, ptr(mask), _i3(size), st.ctypes.data if st.size else None,
+                                                     rt.ctypes.data if rt.size else None, int(rt.size), float(area), float(min_area_mm2),
+                                                     ptr(bits), ptr(counts)), "pp_polar_sectors_u8")
+
+    def resample_bits(self, src, gin, gout, nbits, out, affine_A=None, affine_t=None):
+        """pp_resample_bits_u32: out (uint8 [nbits][Z][Y][X] on gout) plane k = bit k of the uint32 volume `src` (on gin) picked by
+        nearest neighbour through q = A p + t, 0 outside; plane k equals `resample(..., interp=INTERP_NEAREST, u8=True)` of that
+        bit.  ValueError for nbits outside 1 ... 32, a NULL buffer or a geometry the library refuses."""
+        if affine_A is None and affine_t is not None:
+            raise ValueError("resample_bits: a translation needs its matrix (pass the identity)")
+        self._chk_value(self.lib.pp_resample_bits_u32(self.h, ptr(src), C.byref(gin), C.byref(gout), _dn(affine_A, 9), _dn(affine_t, 3),
+                                                      int(nbits), ptr(out)), "pp_resample_bits_u32")
 
     def label_contour(self, mask, size, out):
         self._chk(self.lib.pp_label_contour_u8(self.h, ptr(mask), _i3(size), ptr(out)), "pp_label_contour_u8")

@@ -84,6 +84,32 @@ def shape_statistics_from_moments(moments, spacing, origin, direction):
     return out
 
 
+def principal_axes_from_moments(moments, spacing, direction=(1, 0, 0, 0, 1, 0, 0, 0, 1)):
+    """(principal moments, principal axes) of ONE label from its ten integer sums (a row of label_moments): what
+    sitk.LabelShapeStatisticsImageFilter's GetPrincipalMoments / GetPrincipalAxes report.  The matrix is the one of
+    shape_statistics_from_moments -- the covariance of the voxel centres in physical space plus spacing_i^2 / 12 on the
+    diagonal, rotated by the direction cosines, formed from the int64 sums in exact integer arithmetic --, decomposed with
+    np.linalg.eigh: moments ascending, axes a 3 x 3 array whose ROW k is the unit eigenvector of moment k.  That ITK orders
+    the rows like this (ascending moments, so row 0 is the SHORT axis) is recalled from upstream and UNVERIFIED here, and so
+    is the sign of each row: ITK only fixes the sign of the last row so that the matrix is a proper rotation, an
+    eigenvector's own sign is the eigen-solver's.  A label without voxels raises ValueError."""
+    m = [int(v) for v in np.asarray(moments).reshape(-1)]
+    if len(m) != 10:
+        raise ValueError("principal_axes_from_moments: ten sums {count, x, y, z, xx, yy, zz, xy, xz, yz} expected")
+    n = m[0]
+    if n == 0:
+        raise ValueError("principal_axes_from_moments: the label has no voxels")
+    sp = np.asarray(spacing, dtype=np.float64)
+    d = np.asarray(direction, dtype=np.float64).reshape(3, 3)
+    pairs = {(0, 0): 4, (1, 1): 5, (2, 2): 6, (0, 1): 7, (0, 2): 8, (1, 2): 9}
+    cov = np.zeros((3, 3), dtype=np.float64)
+    for (i, j), s in pairs.items():
+        cov[i, j] = cov[j, i] = (n * m[s] - m[1 + i] * m[1 + j]) / (n * n)      # exact integers, one rounding
+    cov = cov * np.outer(sp, sp) + np.diag(sp * sp / 12.0)
+    lam, vec = np.linalg.eigh(d @ cov @ d.T)
+    return lam, np.ascontiguousarray(vec.T)
+
+
 def label_shape_statistics(label_image, nlabels=None):
     """sitk.LabelShapeStatisticsImageFilter().Execute(label_image) -> {label: {"count", "physical_size", "centroid" (physical,
     x y z), "principal_moments" (ascending), "elongation", "flatness", "roundness": None, "perimeter": None}} for the labels

@@ -16,6 +16,13 @@ class Transform:
     def is_linear(self):
         return True
 
+    def GetInverse(self):
+        """The identity's inverse.  A subclass that is not linear (a displacement field, a B-spline) has no inverse here and
+        raises TypeError rather than inherit this answer; the linear ones override it."""
+        if not self.is_linear():
+            raise TypeError(f"{type(self).__name__}.GetInverse: the transform is not linear and has no inverse here")
+        return Transform()
+
 
 class AffineTransform(Transform):
     """q = A (p - c) + c + t, itk::MatrixOffsetTransformBase (rigid / similarity / affine all reduce to it)."""
@@ -37,6 +44,21 @@ class AffineTransform(Transform):
 
     def GetCenter(self):
         return tuple(self.center)
+
+    def GetInverse(self):
+        """sitk.Transform.GetInverse() of a linear transform (itk::MatrixOffsetTransformBase::GetInverse): the matrix inverted,
+        the centre kept, the translation such that the offset is -A^-1 offset.  Every subclass returns a plain
+        AffineTransform (the inverse of a parametrised transform need not be of its own family).  A singular matrix raises
+        ValueError."""
+        A, off = self.matrix_offset()
+        try:
+            Ai = np.linalg.inv(A)
+        except np.linalg.LinAlgError as e:
+            raise ValueError("GetInverse: the transform's matrix is singular") from e
+        if not np.all(np.isfinite(Ai)):
+            raise ValueError("GetInverse: the transform's matrix is singular")
+        c = self.center
+        return AffineTransform(Ai, -(Ai @ off) - c + Ai @ c, c)
 
     def __repr__(self):
         return f"AffineTransform(matrix={self.matrix.tolist()}, translation={self.translation.tolist()}, center={self.center.tolist()})"
@@ -75,6 +97,15 @@ class CompositeTransform(Transform):
             a, o = t.matrix_offset()
             A, off = a @ A, a @ off + o
         return A, off
+
+    def GetInverse(self):
+        """sitk.CompositeTransform.GetInverse(): the members' inverses in the opposite order.  Defined for linear members; a
+        displacement-field or B-spline member raises TypeError."""
+        parts = self.flatten()
+        for t in parts:
+            if not t.is_linear():
+                raise TypeError(f"CompositeTransform.GetInverse: {type(t).__name__} is not linear and has no inverse here")
+        return CompositeTransform([t.GetInverse() for t in reversed(parts)])
 
     def flatten(self):
         out = []
