@@ -258,6 +258,18 @@ int pp_binary_threshold_f32(pp_ctx* ctx, const float* prob, size_t n, double max
  * component_voxels (host, may be NULL) receives the size of the kept component; non-NULL synchronises. */
 int pp_fillhole_largest_component_u8(pp_ctx* ctx, const uint8_t* in, const int size[3], int fill_holes,
                                      uint8_t* out, int64_t* component_voxels);
+/* The same two steps with a choice of connectivity, each optional (generation/mask.py:77-80, "RelabelComponent(
+ * ConnectedComponent(mask, True)) == 1", and :92, BinaryFillhole(fullyConnected=True)).  fully_connected = 0: faces, as
+ * above; 1: two voxels are neighbours when they differ by at most 1 on every axis.  fill_holes: background components that
+ * do not reach the volume border become foreground; with fully_connected = 1 the BACKGROUND flood from the border is
+ * 26-connected, so a cavity that leaks through a diagonal gap is not a hole [recalled from ITK's GrayscaleFillhole,
+ * unverified here; scipy's binary_fill_holes with a 3 x 3 x 3 structure states the same].  keep_largest: the largest
+ * foreground component, size descending then first in raster order [sitk.RelabelComponent's order as recalled]; no
+ * foreground: the (filled) input comes back.  fill_holes = keep_largest = 0 is PP_ERR_ARG; with fully_connected = 0 and
+ * keep_largest = 1 the result is pp_fillhole_largest_component_u8's, bit for bit.  component_voxels needs keep_largest.
+ * `out` must not alias `in`. */
+int pp_fillhole_largest_component_conn_u8(pp_ctx* ctx, const uint8_t* in, const int size[3], int fill_holes, int keep_largest,
+                                          int fully_connected, uint8_t* out, int64_t* component_voxels);
 
 /* sitk.BinaryDilate / BinaryErode / BinaryMorphologicalClosing(mask, radius) with SimpleITK's defaults
  * (registration/utils.py:328-329; projects/multiatlas/run.py:421-423, projects/cardiac/run.py:1127-1129):
@@ -601,6 +613,14 @@ int pp_tube_mask_u8(pp_ctx* ctx, const double* points, int npoints, const int si
  * be NULL) receives N (GetObjectCount); non-NULL synchronises.  2^31 voxels or more: PP_ERR_SIZE.  Reruns are
  * bit-identical. */
 int pp_connected_components_u8(pp_ctx* ctx, const uint8_t* mask, const int size[3], int32_t* labels, int* count);
+/* sitk.ConnectedComponent(mask, fullyConnected) (generation/mask.py:77).  fully_connected = 0 is
+ * pp_connected_components_u8, bit for bit; with 1 two foreground voxels are joined when they differ by at most 1 on every
+ * axis (13 backward neighbours).  Numbering stays 1 ... N in raster order of each component's first voxel.  The run-based
+ * merge generalises: runs of the four backward rows (dy, dz) = (-1, 0), (0, -1), (-1, -1), (+1, -1) join when their
+ * x-extents overlap after one of them is widened by 1, still tried only where a run starts (and at a run's last voxel, for
+ * the run that starts one past it). */
+int pp_connected_components_conn_u8(pp_ctx* ctx, const uint8_t* mask, const int size[3], int fully_connected, int32_t* labels,
+                                    int* count);
 /* The sums sitk.LabelShapeStatisticsImageFilter derives size, centroid and principal moments from (lung.py:46-56,
  * bronchus.py:221-229, :336-339), for every label in one pass.  labels: DEVICE int32 volume (4-byte aligned); out: DEVICE
  * int64 [nlabels][10] = {count, sum x, sum y, sum z, sum xx, sum yy, sum zz, sum xy, sum xz, sum yz} over the voxel indices of
@@ -621,6 +641,20 @@ int pp_connected_threshold_f32(pp_ctx* ctx, const float* image, const int size[3
  * Neumann condition).  radius (x, y, z) in 0 ... 2, anything else PP_ERR_ARG; `out` must not alias `in`.  From an LDS tile
  * with halo. */
 int pp_binary_median_u8(pp_ctx* ctx, const uint8_t* in, const int size[3], const int radius[3], uint8_t* out);
+
+/* ---- per-slice convex hull (patient external contour) ----------------------------------- */
+/* skimage.morphology.convex_hull_image of every z-slice (generation/mask.py:94-99, a Python loop over the slices).  mask,
+ * out: DEVICE uint8 [Z][Y][X].  For each slice let S be its non-zero pixels (y, x) and P the union over S of the four points
+ * (y +- 1/2, x), (y, x +- 1/2) -- skimage's offset_coordinates=True diamond.  out[z][y][x] = 1 iff the pixel centre (y, x)
+ * lies in the CLOSED convex hull of P: a centre exactly on a hull edge or vertex is inside.  Everything else is 0, every
+ * voxel is written, an empty slice gives zeros.  Exact: doubled integer coordinates and int64 cross products, no floating
+ * point takes part in any decision.  [The rule agrees with scikit-image 0.18.3 on the recorded masks of
+ * tests/golden/slice_convex_hull_skimage_0.18.3.npz; that 0.21.0, which the reference locks, treats boundary centres the
+ * same way is recalled, not verified.]  Row extents, then one workgroup per slice builds the left and right chains and
+ * every row's closed interval, then a fill; `out` may be `mask` itself (in place), any other overlap is not allowed.  An
+ * axis longer than 65535: PP_ERR_SIZE, nothing is launched.  No atomics on global memory, no block waits for another:
+ * reruns are bit-identical. */
+int pp_slice_convex_hull_u8(pp_ctx* ctx, const uint8_t* mask, const int size[3], uint8_t* out);
 
 /* ---- left-ventricle 17-segment model (imaging/utils/ventricle.py) -------------------- */
 /* The segment assignment of generate_left_ventricle_segments (ventricle.py:408-644: a Python loop over slices with 4 or 6

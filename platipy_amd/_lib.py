@@ -175,6 +175,7 @@ _SIGNATURES = {
     "pp_rescale_threshold_f32": (C.c_int, [_P, _P, C.c_size_t, C.c_float, C.c_float, C.c_float]),
     "pp_binary_threshold_f32": (C.c_int, [_P, _P, C.c_size_t, C.c_double, C.c_double, _P]),
     "pp_fillhole_largest_component_u8": (C.c_int, [_P, _P, C.POINTER(C.c_int), C.c_int, _P, C.POINTER(C.c_int64)]),
+    "pp_fillhole_largest_component_conn_u8": (C.c_int, [_P, _P, C.POINTER(C.c_int), C.c_int, C.c_int, C.c_int, _P, C.POINTER(C.c_int64)]),
     "pp_binary_morph_ball_u8": (C.c_int, [_P, _P, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int, _P]),
     "pp_bounding_box": (C.c_int, [_P, _P, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "pp_staple_fuse": (C.c_int, [_P, C.POINTER(_P), C.c_int, C.c_int, C.c_size_t, C.POINTER(StapleParams), _P,
@@ -225,6 +226,8 @@ _SIGNATURES = {
     "pp_tube_mask_u8": (C.c_int, [_P, C.POINTER(C.c_double), C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_double), C.POINTER(C.c_double),
                                   C.c_double, _P]),
     "pp_connected_components_u8": (C.c_int, [_P, _P, C.POINTER(C.c_int), _P, C.POINTER(C.c_int)]),
+    "pp_connected_components_conn_u8": (C.c_int, [_P, _P, C.POINTER(C.c_int), C.c_int, _P, C.POINTER(C.c_int)]),
+    "pp_slice_convex_hull_u8": (C.c_int, [_P, _P, C.POINTER(C.c_int), _P]),
     "pp_label_moments_i32": (C.c_int, [_P, _P, C.POINTER(C.c_int), C.c_int, _P]),
     "pp_connected_threshold_f32": (C.c_int, [_P, _P, C.POINTER(C.c_int), C.c_double, C.c_double, C.POINTER(C.c_int), C.c_int, _P,
                                              C.POINTER(C.c_int64)]),
@@ -310,6 +313,25 @@ def _dn(v, n):
     if v is None:
         return None
     return (C.c_double * n)(*[float(x) for x in v])
+
+
+def _nbytes(buf):
+    """Bytes of a tensor / array, or None for a bare address (nothing to check)."""
+    if buf is None or isinstance(buf, int):
+        return None
+    return buf.numel() * buf.element_size() if hasattr(buf, "numel") else buf.nbytes
+
+
+def _check_volume(who, size, **buffers):
+    """The library gets bare pointers: a buffer that does not have its geometry's size would be read or written past its
+    end.  buffers: name=(buffer, bytes per voxel)."""
+    if len(size) != 3 or min(int(s) for s in size) <= 0:
+        raise ValueError(f"{who}: size must be three positive voxel counts, got {tuple(size)}")
+    n = int(size[0]) * int(size[1]) * int(size[2])
+    for name, (buf, width) in buffers.items():
+        have = _nbytes(buf)
+        if have is not None and have != width * n:
+            raise ValueError(f"{who}: `{name}` does not have the size of its geometry ({have} bytes for {tuple(size)})")
 
 
 def gauss_taps(variance, max_error, max_kernel_width, lib=None):
@@ -666,6 +688,31 @@ class Context:
         self._chk_value(self.lib.pp_connected_components_u8(self.h, ptr(mask), _i3(size), ptr(labels), C.byref(n) if want_count else None),
                         "pp_connected_components_u8")
         return n.value if want_count else None
+
+    def connected_components_conn(self, mask, size, labels, fully_connected=False, want_count=True):
+        """pp_connected_components_conn_u8: connected_components with a choice of connectivity (fully_connected: 26 neighbours)
+        -> the number of components (synchronises), or None without want_count."""
+        _check_volume("connected_components_conn", size, mask=(mask, 1), labels=(labels, 4))
+        n = C.c_int(0)
+        self._chk_value(self.lib.pp_connected_components_conn_u8(self.h, ptr(mask), _i3(size), int(bool(fully_connected)), ptr(labels),
+                                                                 C.byref(n) if want_count else None), "pp_connected_components_conn_u8")
+        return n.value if want_count else None
+
+    def fillhole_largest_component_conn(self, mask, size, out, fill_holes=True, keep_largest=True, fully_connected=False, want_count=False):
+        """pp_fillhole_largest_component_conn_u8: hole filling and / or the largest component with a choice of connectivity ->
+        the kept component's voxels with want_count (synchronises), else None."""
+        _check_volume("fillhole_largest_component_conn", size, mask=(mask, 1), out=(out, 1))
+        n = C.c_int64(0)
+        self._chk_value(self.lib.pp_fillhole_largest_component_conn_u8(self.h, ptr(mask), _i3(size), int(bool(fill_holes)), int(bool(keep_largest)),
+                                                                       int(bool(fully_connected)), ptr(out), C.byref(n) if want_count else None),
+                        "pp_fillhole_largest_component_conn_u8")
+        return n.value if want_count else None
+
+    def slice_convex_hull(self, mask, size, out):
+        """pp_slice_convex_hull_u8: out (uint8 [Z][Y][X]) = the convex hull image of every z-slice of the uint8 mask (`out` may
+        be `mask`).  ValueError for an axis longer than 65535 or a buffer that does not have the size of the volume."""
+        _check_volume("slice_convex_hull", size, mask=(mask, 1), out=(out, 1))
+        self._chk_value(self.lib.pp_slice_convex_hull_u8(self.h, ptr(mask), _i3(size), ptr(out)), "pp_slice_convex_hull_u8")
 
     def label_moments(self, labels, size, nlabels, out):
         """pp_label_moments_i32: out (int64 device memory [nlabels][10]) = {count, sum x, y, z, xx, yy, zz, xy, xz, yz} over the

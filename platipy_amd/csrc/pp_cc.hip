@@ -152,6 +152,26 @@ __global__ void __launch_bounds__(NT) k_cc_rows_wave(const uint8_t* __restrict__
 // Stage 2, across rows: two equal-valued runs in adjacent rows (y - 1 or z - 1) overlap somewhere, and the later
 // of their two starts lies inside the overlap -- one union there joins them, so only positions where either run
 // starts need to try.  That is a few unions per run instead of three per voxel, and finds are one or two hops.
+//
+// FULL (26 neighbours, sitk's fullyConnected = True): the four backward rows (dy, dz) = (-1, 0), (0, -1), (-1, -1), (+1, -1)
+// hold all twelve backward neighbours outside the voxel's own row, and two runs A = [a0, a1], B = [b0, b1] of such a pair of
+// rows are joined when their extents overlap after one is widened by 1: b0 <= a1 + 1 and a0 <= b1 + 1.  The economy holds
+// with one more position: the later start s = max(a0, b0) is inside the widened overlap, so the union is found from row A
+// either at a0 (B covers a0, or ends at a0 - 1), or where B starts over A (b0 in A), or at A's last voxel when B starts at
+// a1 + 1.  cc_join_full is those three tests for the voxel i of A and the voxel j beside it in B's row.
+__device__ __forceinline__ void cc_join_full(const uint8_t* __restrict__ mask, int* L, size_t i, size_t j, int x, int nx, bool v, bool start,
+                                             bool end) {
+  const bool n0 = (mask[j] != 0) == v;
+  const bool nm = x > 0 && (mask[j - 1] != 0) == v;
+  if (n0) {
+    if (start || !nm) cc_unite(L, (int)i, (int)j);
+  } else {
+    if (start && nm) cc_unite(L, (int)i, (int)j - 1);
+    if (end && x + 1 < nx && (mask[j + 1] != 0) == v) cc_unite(L, (int)i, (int)j + 1);
+  }
+}
+
+template <bool FULL>
 __global__ void __launch_bounds__(NT) k_cc_merge(const uint8_t* __restrict__ mask, int* __restrict__ L, pp_dims d, int fg_only) {
   const size_t n = (size_t)d.nx * d.ny * d.nz;
   const int sy = d.nx, sz = d.nx * d.ny;
@@ -161,8 +181,18 @@ __global__ void __launch_bounds__(NT) k_cc_merge(const uint8_t* __restrict__ mas
     const unsigned i32 = (unsigned)i, row = i32 / (unsigned)d.nx;   // (n < 2^31: 32-bit divisions)
     const int x = (int)(i32 - row * (unsigned)d.nx), y = (int)(row % (unsigned)d.ny), z = (int)(row / (unsigned)d.ny);
     const bool start = x == 0 || (mask[i - 1] != 0) != v;
-    if (y > 0 && (mask[i - sy] != 0) == v && (start || (mask[i - sy - 1] != 0) != v)) cc_unite(L, (int)i, (int)i - sy);
-    if (z > 0 && (mask[i - sz] != 0) == v && (start || (mask[i - sz - 1] != 0) != v)) cc_unite(L, (int)i, (int)i - sz);
+    if (!FULL) {
+      if (y > 0 && (mask[i - sy] != 0) == v && (start || (mask[i - sy - 1] != 0) != v)) cc_unite(L, (int)i, (int)i - sy);
+      if (z > 0 && (mask[i - sz] != 0) == v && (start || (mask[i - sz - 1] != 0) != v)) cc_unite(L, (int)i, (int)i - sz);
+    } else {
+      const bool end = x == d.nx - 1 || (mask[i + 1] != 0) != v;
+      if (y > 0) cc_join_full(mask, L, i, i - sy, x, d.nx, v, start, end);
+      if (z > 0) {
+        cc_join_full(mask, L, i, i - sz, x, d.nx, v, start, end);
+        if (y > 0) cc_join_full(mask, L, i, i - sz - sy, x, d.nx, v, start, end);
+        if (y + 1 < d.ny) cc_join_full(mask, L, i, i - sz + sy, x, d.nx, v, start, end);
+      }
+    }
   }
 }
 
@@ -281,7 +311,7 @@ unsigned grid_for(size_t work, unsigned cap = 16384u) {
   return (unsigned)blocks;
 }
 
-int cc_label(pp_ctx* ctx, const uint8_t* mask, int* L, const pp_dims& d, size_t n, int fg_only) {
+int cc_label(pp_ctx* ctx, const uint8_t* mask, int* L, const pp_dims& d, size_t n, int fg_only, int full = 0) {
   const dim3 g(grid_for(n)), b(NT);
   const size_t rows = (size_t)d.ny * d.nz;
   if (pp_env("PP_CC_ROWS_BLOCK")) {   // (the block-per-row form, for A/B runs)
@@ -291,19 +321,17 @@ int cc_label(pp_ctx* ctx, const uint8_t* mask, int* L, const pp_dims& d, size_t 
     hipLaunchKernelGGL(k_cc_rows_wave, dim3((unsigned)(nbr < 16384 ? nbr : 16384)), b, 0, ctx->stream, mask, L, d, fg_only);
   }
   PP_LAUNCH_CHECK(ctx, "k_cc_rows");
-  hipLaunchKernelGGL(k_cc_merge, g, b, 0, ctx->stream, mask, L, d, fg_only);
+  if (full) hipLaunchKernelGGL(k_cc_merge<true>, g, b, 0, ctx->stream, mask, L, d, fg_only);
+  else hipLaunchKernelGGL(k_cc_merge<false>, g, b, 0, ctx->stream, mask, L, d, fg_only);
   PP_LAUNCH_CHECK(ctx, "k_cc_merge");
   hipLaunchKernelGGL(k_cc_compress, g, b, 0, ctx->stream, L, n);
   PP_LAUNCH_CHECK(ctx, "k_cc_compress");
   return PP_OK;
 }
 
-}  // namespace
-
-extern "C" int pp_fillhole_largest_component_u8(pp_ctx* ctx, const uint8_t* in, const int size[3], int fill_holes,
-                                                 uint8_t* out, int64_t* component_voxels) {
-  if (!ctx) return PP_ERR_ARG;
-  pp_device_guard dev_guard_(ctx);
+// fill_holes and / or keep_largest, both with the connectivity `full` (0: faces, 1: faces, edges and corners).
+int cc_fillhole_largest(pp_ctx* ctx, const uint8_t* in, const int size[3], int fill_holes, int keep_largest, int full, uint8_t* out,
+                        int64_t* component_voxels) {
   PP_REQUIRE(ctx, in && out && size, "pp_fillhole_largest_component_u8: NULL argument");
   PP_REQUIRE(ctx, size[0] > 0 && size[1] > 0 && size[2] > 0, "pp_fillhole_largest_component_u8: empty volume");
   const size_t n = pp_nvox(size);
@@ -321,16 +349,18 @@ extern "C" int pp_fillhole_largest_component_u8(pp_ctx* ctx, const uint8_t* in, 
   const dim3 g(grid_for(n)), b(NT);
   const uint8_t* mask = in;
   if (fill_holes) {
-    rc = cc_label(ctx, in, L, d, n, 0);
+    uint8_t* dst = keep_largest ? filled : out;
+    rc = cc_label(ctx, in, L, d, n, 0, full);
     if (rc) return rc;
     PP_HIP(ctx, hipMemsetAsync(aux, 0, n * sizeof(int), ctx->stream));
     hipLaunchKernelGGL(k_cc_flag_border, g, b, 0, ctx->stream, in, (const int*)L, aux, d);
     PP_LAUNCH_CHECK(ctx, "k_cc_flag_border");
-    hipLaunchKernelGGL(k_cc_fill, g, b, 0, ctx->stream, in, (const int*)L, (const int*)aux, filled, n);
+    hipLaunchKernelGGL(k_cc_fill, g, b, 0, ctx->stream, in, (const int*)L, (const int*)aux, dst, n);
     PP_LAUNCH_CHECK(ctx, "k_cc_fill");
     mask = filled;
   }
-  rc = cc_label(ctx, mask, L, d, n, 1);
+  if (!keep_largest) return PP_OK;
+  rc = cc_label(ctx, mask, L, d, n, 1, full);
   if (rc) return rc;
   PP_HIP(ctx, hipMemsetAsync(aux, 0, n * sizeof(int), ctx->stream));
   hipLaunchKernelGGL(k_cc_count, g, b, 0, ctx->stream, mask, (const int*)L, aux, n);
@@ -350,5 +380,25 @@ extern "C" int pp_fillhole_largest_component_u8(pp_ctx* ctx, const uint8_t* in, 
   return PP_OK;
 }
 
+}  // namespace
+
+extern "C" int pp_fillhole_largest_component_u8(pp_ctx* ctx, const uint8_t* in, const int size[3], int fill_holes,
+                                                 uint8_t* out, int64_t* component_voxels) {
+  if (!ctx) return PP_ERR_ARG;
+  pp_device_guard dev_guard_(ctx);
+  return cc_fillhole_largest(ctx, in, size, fill_holes, 1, 0, out, component_voxels);
+}
+
+extern "C" int pp_fillhole_largest_component_conn_u8(pp_ctx* ctx, const uint8_t* in, const int size[3], int fill_holes, int keep_largest,
+                                                      int fully_connected, uint8_t* out, int64_t* component_voxels) {
+  if (!ctx) return PP_ERR_ARG;
+  pp_device_guard dev_guard_(ctx);
+  PP_REQUIRE(ctx, fill_holes || keep_largest, "pp_fillhole_largest_component_conn_u8: nothing to do");
+  PP_REQUIRE(ctx, !component_voxels || keep_largest, "pp_fillhole_largest_component_conn_u8: component_voxels needs keep_largest");
+  return cc_fillhole_largest(ctx, in, size, fill_holes, keep_largest, fully_connected != 0, out, component_voxels);
+}
+
 // connected-component numbering, per-label moments, seeded region growing, binary median: built on cc_label above
 #include "pp_region.h"
+// the per-slice convex hull image (get_external_mask's last step)
+#include "pp_hull.h"

@@ -272,13 +272,7 @@ int rg_volume_args(pp_ctx* ctx, const int* size, const char* who, size_t* n) {
   return PP_OK;
 }
 
-}  // namespace
-
-extern "C" {
-
-int pp_connected_components_u8(pp_ctx* ctx, const uint8_t* mask, const int size[3], int32_t* labels, int* count) {
-  if (!ctx) return PP_ERR_ARG;
-  pp_device_guard dev_guard_(ctx);
+int rg_connected_components(pp_ctx* ctx, const uint8_t* mask, const int size[3], int full, int32_t* labels, int* count) {
   PP_REQUIRE(ctx, mask && size && labels, "pp_connected_components_u8: NULL argument");
   size_t n = 0;
   int rc = rg_volume_args(ctx, size, "pp_connected_components_u8", &n);
@@ -292,7 +286,7 @@ int pp_connected_components_u8(pp_ctx* ctx, const uint8_t* mask, const int size[
   int* chunk = cv.take<int>(nchunks + 1);
   int* total = chunk + nchunks;
   int* L = reinterpret_cast<int*>(labels);
-  rc = cc_label(ctx, mask, L, d, n, 1);
+  rc = cc_label(ctx, mask, L, d, n, 1, full);
   if (rc) return rc;
   const dim3 gc((unsigned)(nchunks < 16384 ? nchunks : 16384)), b(NT);
   hipLaunchKernelGGL(k_rg_root_count, gc, b, 0, ctx->stream, mask, (const int*)L, n, nchunks, chunk);
@@ -310,6 +304,22 @@ int pp_connected_components_u8(pp_ctx* ctx, const uint8_t* mask, const int size[
     *count = h;
   }
   return PP_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int pp_connected_components_u8(pp_ctx* ctx, const uint8_t* mask, const int size[3], int32_t* labels, int* count) {
+  if (!ctx) return PP_ERR_ARG;
+  pp_device_guard dev_guard_(ctx);
+  return rg_connected_components(ctx, mask, size, 0, labels, count);
+}
+
+int pp_connected_components_conn_u8(pp_ctx* ctx, const uint8_t* mask, const int size[3], int fully_connected, int32_t* labels, int* count) {
+  if (!ctx) return PP_ERR_ARG;
+  pp_device_guard dev_guard_(ctx);
+  return rg_connected_components(ctx, mask, size, fully_connected != 0, labels, count);
 }
 
 int pp_label_moments_i32(pp_ctx* ctx, const int32_t* labels, const int size[3], int nlabels, int64_t* out) {

@@ -17,4 +17,4 @@ from .dvf import (  # noqa: F401
     generate_field_shift,
 )
 from .image import insert_cylinder, insert_cylinder_image, insert_sphere, insert_sphere_image  # noqa: F401
-from .mask import extend_mask, get_bone_mask  # noqa: F401
+from .mask import extend_mask, get_bone_mask, get_external_mask  # noqa: F401

@@ -13,14 +13,29 @@ from ..image import as_image
 from .utils import _radius3, _u8
 
 
-def connected_component(mask):
-    """sitk.ConnectedComponent(mask), face connectivity -> (int32 label Image, count): 0 on the background, the components
-    1 ... count in raster order of their first voxel (pp_connected_components_u8)."""
+def connected_component(mask, fully_connected=False):
+    """sitk.ConnectedComponent(mask, fullyConnected) -> (int32 label Image, count): 0 on the background, the components
+    1 ... count in raster order of their first voxel.  Face connectivity by default (pp_connected_components_u8); with
+    fully_connected voxels that touch by an edge or a corner are joined too (pp_connected_components_conn_u8)."""
     mask = as_image(mask)
     src = _u8(mask)
     labels = torch.empty(src.shape, dtype=torch.int32, device=src.device)
-    count = runtime.context(mask.device).connected_components(src, mask.GetSize(), labels)
+    ctx = runtime.context(mask.device)
+    if fully_connected:
+        count = ctx.connected_components_conn(src, mask.GetSize(), labels, fully_connected=True)
+    else:
+        count = ctx.connected_components(src, mask.GetSize(), labels)
     return mask.like(labels), count
+
+
+def slice_convex_hull(mask):
+    """skimage.morphology.convex_hull_image of every z-slice of a binary mask -> uint8 Image on the mask's grid: 1 where the
+    pixel centre lies in the closed convex hull of the slice's pixel diamonds (pp_slice_convex_hull_u8, exact integers)."""
+    mask = as_image(mask)
+    src = _u8(mask)
+    out = torch.empty_like(src)
+    runtime.context(mask.device).slice_convex_hull(src, mask.GetSize(), out)
+    return mask.like(out)
 
 
 def label_moments(label_image, nlabels):

@@ -61,13 +61,30 @@ def binary_morphological_closing(mask, radius):
     return _morph(mask, radius, _CLOSE)
 
 
-def largest_component(mask):
-    """sitk.RelabelComponent(sitk.ConnectedComponent(mask)) == 1 (multiatlas/run.py:421): the largest
-    face-connected component, the first in raster order on ties; an empty mask stays empty."""
+def largest_component(mask, fully_connected=False):
+    """sitk.RelabelComponent(sitk.ConnectedComponent(mask, fully_connected)) == 1 (multiatlas/run.py:421;
+    generation/mask.py:77-80 with fully_connected): the largest component, the first in raster order on ties; an empty
+    mask stays empty."""
     mask = as_image(mask)
     src = _u8(mask)
     out = torch.empty_like(src)
-    runtime.context(mask.device).fillhole_largest_component(src, mask.GetSize(), out, fill_holes=False)
+    ctx = runtime.context(mask.device)
+    if fully_connected:
+        ctx.fillhole_largest_component_conn(src, mask.GetSize(), out, fill_holes=False, keep_largest=True, fully_connected=True)
+    else:
+        ctx.fillhole_largest_component(src, mask.GetSize(), out, fill_holes=False)
+    return mask.like(out)
+
+
+def binary_fillhole(mask, fully_connected=False):
+    """sitk.BinaryFillhole(mask, fullyConnected): background that is not connected to the image border becomes foreground.
+    fully_connected is the connectivity of that BACKGROUND flood: with it a cavity that reaches the outside through a
+    diagonal gap is not a hole (generation/mask.py:92)."""
+    mask = as_image(mask)
+    src = _u8(mask)
+    out = torch.empty_like(src)
+    runtime.context(mask.device).fillhole_largest_component_conn(src, mask.GetSize(), out, fill_holes=True, keep_largest=False,
+                                                                fully_connected=bool(fully_connected))
     return mask.like(out)
 
 
