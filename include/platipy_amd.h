@@ -580,6 +580,31 @@ int pp_bspline_metric_f32(pp_ctx* ctx, int metric, const float* fixed, const pp_
                           const uint8_t* moving_mask, const float* coefficients, const pp_geom* lattice,
                           double jitter_bound, double* value, double* stats, double* gradient);
 
+/* Mattes mutual information over the B-spline (SetMetricAsMattesMutualInformation(numberOfHistogramBins) at reference
+ * deformable.py:482-485), in two passes as pp_mi_histogram_f32 / pp_mi_gradient_f32 are for the affine case.  Samples, their
+ * validity, jitter, masks, the moving-gradient source, jitter_bound, the direction rule and stats[4] are exactly those of
+ * pp_bspline_metric_f32; `bins` must be PP_MI_MATTES with 5..64 bins (PP_ERR_ARG otherwise).
+ * Pass 1: hist[nbins * nbins] (HOST, row = fixed bin) = the joint histogram of the valid samples, fixed intensity in its
+ * nearest bin, moving intensity spread over 4 bins by the cubic B-spline, every weight accumulated in 64-bit fixed point
+ * (2^-32 units) with integer atomics: two calls return identical bits.  The caller turns it into the value and a score
+ * table (platipy_amd/registration/_mattes.py).  A refusal (PP_ERR_ARG, PP_ERR_DIRECTION, a sample beyond jitter_bound,
+ * PP_ERR_NO_OVERLAP) leaves hist and stats untouched.  Synchronises. */
+int pp_bspline_mi_histogram_f32(pp_ctx* ctx, const float* fixed, const pp_geom* fixed_geom, const float* moving,
+                                const pp_geom* moving_geom, const pp_geom* virt, int stride, const uint8_t* fixed_mask,
+                                const uint8_t* moving_mask, const float* coefficients, const pp_geom* lattice,
+                                double jitter_bound, const pp_mi_bins* bins, double* hist, double* stats);
+/* Pass 2 (reference deformable.py:482-485, the derivative ITK's metric hands to the optimiser at :513): gradient[3 cx cy cz]
+ * (HOST, ITK's flat parameter order), for coefficient p = (r, k, j, i)
+ *   sum_s [ sum_{q = mb_s - 1 .. mb_s + 2} B3'(q - tm_s) table[fb_s][q] ] (g_s . Md)_r w_i w_j w_k
+ * over the valid samples inside the transform domain whose 4 x 4 x 4 support holds the control point.  table[nbins * nbins]
+ * (HOST, fp64; held as fp32 on the device) already carries 1 / (N m_bin): no further normalisation.  No floating-point
+ * atomics: two calls return identical bits.  A refusal leaves stats and gradient untouched.  Synchronises. */
+int pp_bspline_mi_gradient_f32(pp_ctx* ctx, const float* fixed, const pp_geom* fixed_geom, const float* moving,
+                               const pp_geom* moving_geom, const pp_geom* virt, int stride, const uint8_t* fixed_mask,
+                               const uint8_t* moving_mask, const float* coefficients, const pp_geom* lattice,
+                               double jitter_bound, const pp_mi_bins* bins, const double* table, double* stats,
+                               double* gradient);
+
 /* ---- vessel splining --------------------------------------------------------------- */
 /* The per-slice sums behind com_from_image_list (imaging/utils/vessel.py:33-167) and get_com (label/utils.py:61-84), for
  * every atlas's propagated label in one pass.  masks: HOST array of nmasks (1 ... 64) device pointers to uint8 volumes of

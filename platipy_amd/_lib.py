@@ -222,6 +222,12 @@ _SIGNATURES = {
     "pp_bspline_metric_f32": (C.c_int, [_P, C.c_int, _P, C.POINTER(Geom), _P, C.POINTER(Geom), C.POINTER(Geom), C.c_int, _P, _P, _P,
                                         C.POINTER(Geom), C.c_double, C.POINTER(C.c_double), C.POINTER(C.c_double),
                                         C.POINTER(C.c_double)]),
+    "pp_bspline_mi_histogram_f32": (C.c_int, [_P, _P, C.POINTER(Geom), _P, C.POINTER(Geom), C.POINTER(Geom), C.c_int, _P, _P, _P,
+                                              C.POINTER(Geom), C.c_double, C.POINTER(MiBins), C.POINTER(C.c_double),
+                                              C.POINTER(C.c_double)]),
+    "pp_bspline_mi_gradient_f32": (C.c_int, [_P, _P, C.POINTER(Geom), _P, C.POINTER(Geom), C.POINTER(Geom), C.c_int, _P, _P, _P,
+                                             C.POINTER(Geom), C.c_double, C.POINTER(MiBins), C.POINTER(C.c_double),
+                                             C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "pp_slice_moments_u8": (C.c_int, [_P, C.POINTER(_P), C.c_int, C.POINTER(C.c_int), C.c_int, _P]),
     "pp_tube_mask_u8": (C.c_int, [_P, C.POINTER(C.c_double), C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_double), C.POINTER(C.c_double),
                                   C.c_double, _P]),
@@ -472,17 +478,66 @@ class Context:
         self._chk(self.lib.pp_bspline_field_f32(self.h, ptr(coefficients), C.byref(lattice_geom), C.byref(grid_geom), ptr(out)),
                   "pp_bspline_field_f32")
 
+    @staticmethod
+    def _bspline_buffer_check(name, fixed, fixed_geom, moving, moving_geom, fixed_mask, moving_mask, coefficients, lattice_geom):
+        """-> the number of coefficients.  The library gets bare pointers: a buffer that does not have its geometry's size would
+        be read past its end."""
+        for what, buf, g, width in (("fixed", fixed, fixed_geom, 4), ("moving", moving, moving_geom, 4), ("fixed_mask", fixed_mask, fixed_geom, 1),
+                                    ("moving_mask", moving_mask, moving_geom, 1), ("coefficients", coefficients, lattice_geom, 12)):
+            have = None if buf is None or isinstance(buf, int) else (buf.numel() * buf.element_size() if hasattr(buf, "numel") else buf.nbytes)
+            if have is not None and have != width * int(g.size[0]) * int(g.size[1]) * int(g.size[2]):
+                raise ValueError(f"{name}: `{what}` does not have the size of its geometry")
+        return 3 * int(lattice_geom.size[0]) * int(lattice_geom.size[1]) * int(lattice_geom.size[2])
+
+    def _bspline_raise(self, name, rc):
+        msg = self.lib.pp_last_error(self.h)
+        err = PlatipyAmdError(f"{name} failed ({rc}): {msg.decode(errors='replace') if msg else ''}")
+        err.code = rc
+        raise err
+
+    def bspline_mi_histogram(self, fixed, fixed_geom, moving, moving_geom, virtual_geom, stride, coefficients, lattice_geom, bins,
+                             fixed_mask=None, moving_mask=None, jitter_bound=0.0):
+        """pp_bspline_mi_histogram_f32 -> (hist [nbins, nbins] float64, row = fixed bin; stats dict).  Raises PlatipyAmdError with
+        .code (ERR_DIRECTION, ERR_NO_OVERLAP, ...)."""
+        self._bspline_buffer_check("bspline_mi_histogram", fixed, fixed_geom, moving, moving_geom, fixed_mask, moving_mask, coefficients,
+                                   lattice_geom)
+        if not 1 <= int(bins.nbins) <= 64:      # the output array is sized from it
+            raise ValueError("bspline_mi_histogram: 5..64 bins")
+        hist = np.zeros((int(bins.nbins), int(bins.nbins)), dtype=np.float64)
+        st = (C.c_double * 4)()
+        rc = self.lib.pp_bspline_mi_histogram_f32(self.h, ptr(fixed), C.byref(fixed_geom), ptr(moving), C.byref(moving_geom),
+                                                  C.byref(virtual_geom), int(stride), ptr(fixed_mask), ptr(moving_mask), ptr(coefficients),
+                                                  C.byref(lattice_geom), float(jitter_bound), C.byref(bins),
+                                                  hist.ctypes.data_as(C.POINTER(C.c_double)), st)
+        if rc:
+            self._bspline_raise("pp_bspline_mi_histogram_f32", rc)
+        return hist, {"valid": st[0], "outside": st[1], "masked": st[2], "seen": st[3]}
+
+    def bspline_mi_gradient(self, fixed, fixed_geom, moving, moving_geom, virtual_geom, stride, coefficients, lattice_geom, bins, table,
+                            fixed_mask=None, moving_mask=None, jitter_bound=0.0):
+        """pp_bspline_mi_gradient_f32 with the score `table` [nbins, nbins] -> (float64 gradient [3 cx cy cz] in ITK's parameter
+        order, stats dict)."""
+        n = self._bspline_buffer_check("bspline_mi_gradient", fixed, fixed_geom, moving, moving_geom, fixed_mask, moving_mask, coefficients,
+                                       lattice_geom)
+        tab = np.ascontiguousarray(table, dtype=np.float64)
+        if tab.size != int(bins.nbins) ** 2:
+            raise ValueError("bspline_mi_gradient: `table` is not nbins x nbins")
+        grad = np.zeros(n, dtype=np.float64)
+        st = (C.c_double * 4)()
+        rc = self.lib.pp_bspline_mi_gradient_f32(self.h, ptr(fixed), C.byref(fixed_geom), ptr(moving), C.byref(moving_geom),
+                                                 C.byref(virtual_geom), int(stride), ptr(fixed_mask), ptr(moving_mask), ptr(coefficients),
+                                                 C.byref(lattice_geom), float(jitter_bound), C.byref(bins),
+                                                 tab.ctypes.data_as(C.POINTER(C.c_double)), st, grad.ctypes.data_as(C.POINTER(C.c_double)))
+        if rc:
+            self._bspline_raise("pp_bspline_mi_gradient_f32", rc)
+        return grad, {"valid": st[0], "outside": st[1], "masked": st[2], "seen": st[3]}
+
     def bspline_metric(self, metric, fixed, fixed_geom, moving, moving_geom, virtual_geom, stride, coefficients, lattice_geom,
                        fixed_mask=None, moving_mask=None, jitter_bound=0.0):
         """pp_bspline_metric_f32 -> (value, float64 gradient [3 cx cy cz] in ITK's parameter order, stats dict).  Raises
         PlatipyAmdError with .code (ERR_DIRECTION, ERR_NO_OVERLAP, ...)."""
-        n = 3 * int(lattice_geom.size[0]) * int(lattice_geom.size[1]) * int(lattice_geom.size[2])
-        for what, buf, g, width in (("fixed", fixed, fixed_geom, 4), ("moving", moving, moving_geom, 4), ("fixed_mask", fixed_mask, fixed_geom, 1),
-                                    ("moving_mask", moving_mask, moving_geom, 1), ("coefficients", coefficients, lattice_geom, 12)):
-            # the library gets bare pointers: a buffer that does not have its geometry's size would be read past its end
-            have = None if buf is None or isinstance(buf, int) else (buf.numel() * buf.element_size() if hasattr(buf, "numel") else buf.nbytes)
-            if have is not None and have != width * int(g.size[0]) * int(g.size[1]) * int(g.size[2]):
-                raise ValueError(f"bspline_metric: `{what}` does not have the size of its geometry")
+        n = self._bspline_buffer_check("bspline_metric", fixed, fixed_geom, moving, moving_geom, fixed_mask, moving_mask, coefficients,
+                                       lattice_geom)
         grad = np.zeros(n, dtype=np.float64)
         value = C.c_double()
         st = (C.c_double * 4)()

@@ -1214,7 +1214,7 @@ __global__ void __launch_bounds__(NT) k_metric_grad(const float* __restrict__ F,
 // PP_MI_MATTES: fixed intensity to its nearest bin, moving intensity spread over 4 bins with a cubic B-spline Parzen
 // window (itk::MattesMutualInformationImageToImageMetricv4); PP_MI_JOINT: both to their nearest bin, score differenced
 // between the two neighbouring moving-bin centres (joint-histogram MI; the PDF smoothing is the host's).
-constexpr int MI_MAX_BINS = 64;
+// (MI_MAX_BINS, mi_bspline3, mi_bspline3_deriv and mi_bin are in pp_internal.h: the B-spline metric of pp_bspline.h bins the same way)
 struct mi_args {
   double Af[9], bf[3], Am[9], bm[3];
   int vsize[3];
@@ -1224,19 +1224,6 @@ struct mi_args {
   const float* jit;   // (as msq_args)
   const float* grad;  // (as msq_args)
 };
-
-__device__ __forceinline__ double mi_bspline3(double u) {   // cubic B-spline, support (-2, 2)
-  const double a = fabs(u);
-  if (a < 1.0) return (4.0 - 6.0 * a * a + 3.0 * a * a * a) / 6.0;
-  if (a < 2.0) { const double t = 2.0 - a; return t * t * t / 6.0; }
-  return 0.0;
-}
-__device__ __forceinline__ double mi_bspline3_deriv(double u) {
-  const double a = fabs(u), sg = u < 0.0 ? -1.0 : 1.0;
-  if (a < 1.0) return sg * (-2.0 * a + 1.5 * a * a);
-  if (a < 2.0) { const double t = 2.0 - a; return sg * (-0.5 * t * t); }
-  return 0.0;
-}
 
 // -> valid; f / m values (trilinear), moving interpolant gradient (moving index units), virtual index v
 __device__ __forceinline__ bool mi_sample(const float* __restrict__ F, const pp_dims& df, const float* __restrict__ M, const pp_dims& dm,
@@ -1285,13 +1272,6 @@ __device__ __forceinline__ bool mi_sample(const float* __restrict__ F, const pp_
   g[2] = v1 - v0;
   if (a.grad) msq_gradient_image(a.grad, dm, x0, x1, y0, y1, z0, z1, wx, wy, wz, g);   // (uniform; see msq_gradient_image)
   return true;
-}
-
-// bin of an intensity: nearest (zero-order) index clamped to [lo, hi], and the continuous bin coordinate
-__device__ __forceinline__ int mi_bin(double value, double bin, double norm_min, int lo, int hi, double& term) {
-  term = value / bin - norm_min;
-  int i = (int)floor(term);
-  return i < lo ? lo : (i > hi ? hi : i);
 }
 
 __global__ void __launch_bounds__(NT) k_mi_histogram(const float* __restrict__ F, pp_dims df, const float* __restrict__ M, pp_dims dm,

@@ -292,6 +292,29 @@ __device__ __forceinline__ float pp_trilinear(const T* __restrict__ im, int nx, 
   return v0 + (v1 - v0) * wz;
 }
 
+// Bin rules of the mutual-information metrics (pp_mi_histogram_f32 / pp_mi_gradient_f32 in pp_fusion.hip and their B-spline
+// counterparts in pp_bspline.h): at most MI_MAX_BINS bins, the cubic B-spline Parzen window and its derivative, and the bin
+// of an intensity.
+constexpr int MI_MAX_BINS = 64;
+__device__ __forceinline__ double mi_bspline3(double u) {   // cubic B-spline, support (-2, 2)
+  const double a = fabs(u);
+  if (a < 1.0) return (4.0 - 6.0 * a * a + 3.0 * a * a * a) / 6.0;
+  if (a < 2.0) { const double t = 2.0 - a; return t * t * t / 6.0; }
+  return 0.0;
+}
+__device__ __forceinline__ double mi_bspline3_deriv(double u) {
+  const double a = fabs(u), sg = u < 0.0 ? -1.0 : 1.0;
+  if (a < 1.0) return sg * (-2.0 * a + 1.5 * a * a);
+  if (a < 2.0) { const double t = 2.0 - a; return sg * (-0.5 * t * t); }
+  return 0.0;
+}
+// bin of an intensity: nearest (zero-order) index clamped to [lo, hi], and the continuous bin coordinate
+__device__ __forceinline__ int mi_bin(double value, double bin, double norm_min, int lo, int hi, double& term) {
+  term = value / bin - norm_min;
+  int i = (int)floor(term);
+  return i < lo ? lo : (i > hi ? hi : i);
+}
+
 // The same sample with the two x corners of each row fetched as ONE access of 2 sizeof(T) bytes from an element-aligned
 // position (global accesses run in unaligned mode on gfx950): a gather's cost is its memory instructions, and this
 // halves them.  The pair starts at min(x0, nx - 2); on the last index -- where ITK's upper corner repeats the lower one

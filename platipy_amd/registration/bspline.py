@@ -1,9 +1,10 @@
 """Drop-in for platipy/imaging/registration/deformable.py:309-547 (bspline_registration).
 
 What the reference hands to sitk.ImageRegistrationMethod with a sitk.BSplineTransform as the optimised transform is rebuilt
-around two GPU kernels: the dense evaluation of the transform (pp_bspline_field_f32) and the similarity metric with its
-gradient over all 3 cx cy cz control-point coefficients (pp_bspline_metric_f32: one workgroup per B-spline cell, no
-floating-point atomics, bit-identical between calls).  Levels (shrink factors, smoothing in physical units, REGULAR sampling
+around the dense evaluation of the transform (pp_bspline_field_f32) and the similarity metric with its gradient over all
+3 cx cy cz control-point coefficients (pp_bspline_metric_f32 for mean squares and correlation; pp_bspline_mi_histogram_f32 and
+pp_bspline_mi_gradient_f32 for Mattes mutual information: one workgroup per B-spline cell, no floating-point atomics,
+bit-identical between calls).  Levels (shrink factors, smoothing in physical units, REGULAR sampling
 with ITK's seeded jitter, the filtered moving-gradient image) are the linear module's; the optimisers run on the host over
 the flat parameter vector, as they do in ITK.
 
@@ -24,7 +25,13 @@ Deliberate deviations:
     1e-4 and lineSearchAccuracy 0.01); the delta-convergence test (tolerance 0.01 over a distance of 0 = off) is not restated;
   * optimiser "lbfgsb" is scipy's fmin_l_bfgs_b as the linear module calls it (m = 5, factr = 1e7, pgtol = 1e-5,
     maxfun = 1024, no bounds), ITK's being the same Fortran code behind another wrapper;
-  * "cgls", and the metrics "mutual_information" and "demons", raise NotImplementedError (see bspline_registration);
+  * Mattes mutual information (the reference's metric="mutual_information", deformable.py:482-485) is spelled
+    metric="mattes_mi", as linear_registration spells the same ITK metric; the reference's spelling keeps raising
+    NotImplementedError, with a message that names "mattes_mi" -- the arrangement the project already has for
+    vote_type="patch_correlation" and fusion.mutual_information.  number_of_histogram_bins_mi must lie in 5..64.  The histogram
+    is accumulated in 64-bit fixed point (units of 2^-32 per weight), the bins' intensity range is that of each level's
+    smoothed image inside its structure when one is given;
+  * "cgls" and the metric "demons" raise NotImplementedError (see bspline_registration);
   * fixed_structure / moving_structure on another grid than their image (always so with isotropic_resample) are resampled onto
     it, nearest neighbour; None means "no mask" as False does;
   * a level whose trial point leaves the overlap reports a large value with a zero gradient to the quasi-Newton optimisers
@@ -36,10 +43,11 @@ import torch
 from .. import _lib, runtime
 from ..image import as_image, cast_tensor
 from ..transform import BSplineTransform, bspline_transform_initializer, sitkBSpline, sitkNearestNeighbor
+from . import _mattes
 from . import linear as _linear
 from .utils import apply_transform, control_point_spacing_distance_to_number, discrete_gaussian, smooth_and_resample
 
-_METRICS = {"mean_squares": _lib.BSPLINE_MEAN_SQUARES, "correlation": _lib.BSPLINE_CORRELATION}
+_METRICS = {"mean_squares": _lib.BSPLINE_MEAN_SQUARES, "correlation": _lib.BSPLINE_CORRELATION, "mattes_mi": None}
 _OPTIMISERS = ("lbfgsb", "lbfgs", "cgls", "gradient_descent", "gradient_descent_line_search")
 REFINE_PADDING = 12     # control points added on every side of the fine lattice before the prefilter (refine_bspline)
 
@@ -96,9 +104,11 @@ def refine_bspline(transform, mesh_size):
 
 
 class _BSplineMetric:
-    """value / gradient of one level's similarity metric over the flat coefficient vector (pp_bspline_metric_f32)."""
+    """value / gradient of one level's similarity metric over the flat coefficient vector: pp_bspline_metric_f32, or -- with
+    `mi_bins`, the number of histogram bins of "mattes_mi" -- pp_bspline_mi_histogram_f32, the host's score table
+    (_mattes.value_and_table) and pp_bspline_mi_gradient_f32.  A value alone costs the histogram pass only."""
 
-    def __init__(self, ctx, metric, fixed, moving, virtual, stride, transform, fixed_mask, moving_mask, jitter_bound):
+    def __init__(self, ctx, metric, fixed, moving, virtual, stride, transform, fixed_mask, moving_mask, jitter_bound, mi_bins=None):
         self.ctx, self.metric = ctx, metric
         self.ft = (fixed.tensor if fixed.tensor.dtype == torch.float32 else fixed.tensor.float()).contiguous()
         self.mt = (moving.tensor if moving.tensor.dtype == torch.float32 else moving.tensor.float()).contiguous()
@@ -117,6 +127,12 @@ class _BSplineMetric:
         self.jitter_bound = float(jitter_bound)
         self.evaluations = 0
         self.last = None
+        self.bins = None
+        self.last_hist = None       # mutual information: (x, value, score table) of the last histogram pass
+        if mi_bins is not None:
+            # the range of the level's smoothed images, inside their masks when there are any (as linear_registration's levels)
+            self.bins = _mattes.make_bins(int(mi_bins), _lib.MI_MATTES, _mattes.intensity_range(ctx, self.ft, self.fmask),
+                                          _mattes.intensity_range(ctx, self.mt, self.mmask))
 
     def coefficients(self, x):
         return torch.from_numpy(np.asarray(x, dtype=np.float32).reshape(self.shape)).to(self.device).contiguous()
@@ -128,8 +144,13 @@ class _BSplineMetric:
             return self.last[1], self.last[2]
         self.evaluations += 1
         try:
-            v, g, _ = self.ctx.bspline_metric(self.metric, self.ft, self.fg, self.mt, self.mg, self.vg, self.stride, self.coefficients(x),
-                                              self.lg, self.fmask, self.mmask, self.jitter_bound)
+            if self.bins is not None:
+                v, table = self._mi_value_and_table(x)
+                g, _ = self.ctx.bspline_mi_gradient(self.ft, self.fg, self.mt, self.mg, self.vg, self.stride, self.coefficients(x), self.lg,
+                                                    self.bins, table, self.fmask, self.mmask, self.jitter_bound)
+            else:
+                v, g, _ = self.ctx.bspline_metric(self.metric, self.ft, self.fg, self.mt, self.mg, self.vg, self.stride, self.coefficients(x),
+                                                  self.lg, self.fmask, self.mmask, self.jitter_bound)
         except _lib.PlatipyAmdError as e:
             if getattr(e, "code", None) == _lib.ERR_NO_OVERLAP:
                 raise RuntimeError("bspline registration: no valid sample points (images do not overlap)") from e
@@ -137,8 +158,25 @@ class _BSplineMetric:
         self.last = (np.array(x, dtype=np.float64), v, g)
         return v, g
 
+    def _mi_value_and_table(self, x):
+        """The histogram pass at x (kept: the gradient pass at the same point reuses it) -> (value, score table)."""
+        if self.last_hist is None or not np.array_equal(self.last_hist[0], x):
+            hist, stats = self.ctx.bspline_mi_histogram(self.ft, self.fg, self.mt, self.mg, self.vg, self.stride, self.coefficients(x), self.lg,
+                                                        self.bins, self.fmask, self.mmask, self.jitter_bound)
+            self.last_hist = (np.array(x, dtype=np.float64),) + _mattes.value_and_table("mattes_mi", hist, stats["valid"], self.bins.m_bin)
+        return self.last_hist[1], self.last_hist[2]
+
     def value(self, x):
-        return self.value_and_gradient(x)[0]
+        if self.bins is None or (self.last is not None and np.array_equal(self.last[0], x)):
+            return self.value_and_gradient(x)[0]
+        if self.last_hist is None or not np.array_equal(self.last_hist[0], x):
+            self.evaluations += 1
+        try:
+            return self._mi_value_and_table(x)[0]
+        except _lib.PlatipyAmdError as e:
+            if getattr(e, "code", None) == _lib.ERR_NO_OVERLAP:
+                raise RuntimeError("bspline registration: no valid sample points (images do not overlap)") from e
+            raise
 
     def values(self, xs):
         out = []
@@ -232,13 +270,16 @@ def bspline_registration(
 ):
     """B-spline (free-form deformation) registration (reference registration/deformable.py:309-547).
 
-    -> (registered_image, BSplineTransform).  Arguments and defaults are the reference's; `ncores` is accepted and ignored (the
+    -> (registered_image, BSplineTransform).  Arguments and defaults are the reference's; metric: "mean_squares", "correlation" or
+    "mattes_mi" (Mattes mutual information with number_of_histogram_bins_mi bins, 5..64 -- the reference's "mutual_information",
+    spelled as linear_registration spells it; the reference's spelling raises NotImplementedError and says so); `ncores` is accepted and ignored (the
     work runs on the GPU); `itk_sampling` as in linear_registration: True moves every sample point by ITK's seeded jitter and
     takes the moving gradient from ITK's filtered gradient image, False samples on the lattice with the analytic gradient of
     the trilinear interpolant.  The returned transform carries `.level_values`: the (first, last) metric value of each level."""
     opt = str(optimiser).lower()
     if metric == "mutual_information":
-        raise NotImplementedError("bspline_registration: Mattes mutual information over a B-spline transform is not built yet")
+        raise NotImplementedError('bspline_registration: Mattes mutual information over a B-spline transform is metric="mattes_mi" '
+                                  "(the spelling linear_registration uses for the same ITK metric)")
     if metric == "demons":
         raise NotImplementedError("bspline_registration: ITK's demons metric (v4) accepts displacement-field transforms only and so "
                                   "rejects a B-spline transform [ITK-upstream, unverified here]")
@@ -248,6 +289,12 @@ def bspline_registration(
         raise ValueError(f"bspline_registration: unknown optimiser {optimiser!r}")
     if opt == "cgls":
         raise NotImplementedError("bspline_registration: the conjugate-gradient line-search optimiser (cgls) is not built yet")
+    mi_bins = None
+    if metric == "mattes_mi":
+        mi_bins = int(number_of_histogram_bins_mi)
+        if not 5 <= mi_bins <= 64:
+            raise ValueError(f"bspline_registration: number_of_histogram_bins_mi must be in 5..64 (2 padding bins on either side, at most "
+                             f"64 x 64 bins in the kernels' LDS table), got {number_of_histogram_bins_mi}")
     levels = len(resolution_staging)
     if len(smooth_sigmas) != levels or len(grid_scale_factors) != levels:
         raise ValueError("bspline_registration: resolution_staging, smooth_sigmas and grid_scale_factors need one entry per level")
@@ -301,7 +348,8 @@ def bspline_registration(
                 if grad.is_cuda and int(np.prod(vsize)) / stride >= _linear.PACKED_GRADIENT_MIN_SAMPLES:      # for the copy, as linear.py
                     packed = torch.stack((grad[0], grad[1], grad[2], m_l.tensor.float()), dim=-1)
                 ctx.set_moving_gradient(grad, packed=packed)
-            ms = _BSplineMetric(ctx, _METRICS[metric], f_l, m_l, virtual, stride, transform, fixed_mask, moving_mask, jitter_bound)
+            ms = _BSplineMetric(ctx, _METRICS[metric], f_l, m_l, virtual, stride, transform, fixed_mask, moving_mask, jitter_bound,
+                                mi_bins=mi_bins)
             x = np.asarray(transform.coefficients.detach().reshape(-1).cpu().numpy(), dtype=np.float64)
             first = ms.value(x)
             if verbose:

@@ -56,6 +56,7 @@ from ..transform import (
     VersorRigid3DTransform,
     _Parametrised,
 )
+from . import _mattes
 from .utils import apply_transform, discrete_gaussian
 
 _MODELS = {
@@ -141,30 +142,13 @@ class _MeanSquares:
         self.evaluations = 0
         self.bins = None
         if metric in MI_BINS:
-            from .._lib import MI_JOINT, MI_MATTES, MiBins
+            from .._lib import MI_JOINT, MI_MATTES
 
-            nb, pad = MI_BINS[metric], 2
-            # intensity range of each image INSIDE its mask when one is given (both ITK v4 MI metrics' Initialize() walk
-            # the image and skip points outside the mask); an empty mask leaves the whole image
-            f_lo, f_hi = self._intensity_range(ctx, self.ft, self.fmask)
-            m_lo, m_hi = self._intensity_range(ctx, self.mt, self.mmask)
-            b = MiBins()
-            b.nbins, b.kernel = nb, (MI_MATTES if metric == "mattes_mi" else MI_JOINT)
-            # itk::MattesMutualInformation...::Initialize: bin = (max - min) / (bins - 2 padding), normalised min = min / bin - padding
-            b.f_bin = max((f_hi - f_lo) / (nb - 2 * pad), 1e-30)
-            b.m_bin = max((m_hi - m_lo) / (nb - 2 * pad), 1e-30)
-            b.f_norm_min = f_lo / b.f_bin - pad
-            b.m_norm_min = m_lo / b.m_bin - pad
-            self.bins = b
+            # intensity range of each image INSIDE its mask when one is given (_mattes.intensity_range)
+            self.bins = _mattes.make_bins(MI_BINS[metric], MI_MATTES if metric == "mattes_mi" else MI_JOINT,
+                                          self._intensity_range(ctx, self.ft, self.fmask), self._intensity_range(ctx, self.mt, self.mmask))
 
-    @staticmethod
-    def _intensity_range(ctx, image, mask):
-        if mask is not None:
-            inside = mask != 0
-            if bool(inside.any()):
-                inf = torch.tensor(float("inf"), dtype=image.dtype, device=image.device)
-                return float(torch.where(inside, image, inf).min()), float(torch.where(inside, image, -inf).max())
-        return ctx.minmax(image, image.numel())
+    _intensity_range = staticmethod(_mattes.intensity_range)
 
     def total(self, model, params):
         """(A, off) of initial o model(params): q = A p + off."""
@@ -213,26 +197,8 @@ class _MeanSquares:
 
     def _mi_value_and_table(self, hist, count):
         """Joint histogram -> (negative mutual information, per-bin score table for the gradient pass)."""
-        eps = 1e-16
-        if self.metric == "mattes_mi":
-            P = hist / hist.sum()
-        else:
-            from scipy.ndimage import correlate1d
-
-            from .._lib import gauss_taps
-
-            taps = np.asarray(gauss_taps(JOINT_PDF_SMOOTHING_VARIANCE, 0.01, 32, lib=self.ctx.lib))   # ITK's DiscreteGaussian on the PDF image
-            P = correlate1d(correlate1d(hist / count, taps, axis=0, mode="nearest"), taps, axis=1, mode="nearest")
-        PF, PM = P.sum(1), P.sum(0)
-        ok = (P > eps) & (PF[:, None] > eps) & (PM[None, :] > eps)
-        safe = np.where(ok, P, 1.0)
-        value = -float((np.where(ok, P * np.log(safe / np.where(ok, PF[:, None] * PM[None, :], 1.0)), 0.0)).sum())
-        ratio = np.where(ok, np.log(safe / np.where(ok, np.broadcast_to(PM[None, :], P.shape), 1.0)), 0.0)
-        # Mattes: d value / d mu = sum_s sum_k B3'(k - u_s) table[f_s][k] (grad M . dT/dmu), table = log(P / PM) / (N bin)
-        # joint:  d value / d mu = -(1/N) sum_s d/dm [log P - log PM](f_s, m_s) (grad M . dT/dmu), differenced between bin centres
-        scale = 1.0 / (count * self.bins.m_bin)
-        table = ratio * scale if self.metric == "mattes_mi" else -ratio * scale
-        return value, table
+        return _mattes.value_and_table(self.metric, hist, count, self.bins.m_bin, lib=self.ctx.lib,
+                                       smoothing_variance=JOINT_PDF_SMOOTHING_VARIANCE)
 
     def value(self, model, params):
         return self.raw(model, params)[0] if self.bins is None else self.values(model, [params])[0]

@@ -1,11 +1,15 @@
 """Time the two B-spline kernels at 512 x 512 x 256 (1 mm), meshes 8 x 8 x 4 and 32 x 32 x 16, against the same quantities
-composed from torch: separable einsum evaluation of the field; grid_sample + index_add_ for the mean-squares gradient.
+composed from torch: separable einsum evaluation of the field; grid_sample + index_add_ for the mean-squares gradient.  Beside
+the mean-squares evaluation: the two passes of Mattes mutual information (30 bins) and one whole evaluation (histogram pass,
+the host's score table, gradient pass), with their ratio to the mean-squares evaluation of the same run.  --baseline-lib PATH
+times the mean-squares evaluation of another build of the library (the parent commit's, say) in the same run on the same box.
 
 HIP-event times, medians over --repeats after --warmup launches, buffers allocated once, a 512 MB scrub between timed launches
 so no launch starts with its inputs in Infinity Cache.  Writes profiles/bspline_bench.json; the bytes/voxel "requested" beside the compulsory bytes are modelled from the access
 pattern, not read from counters.  For the per-kernel view run it under `rocprofv3 --kernel-trace --stats -- python
 tools/bspline_bench.py --repeats 3` and keep the stats file beside the JSON."""
 import argparse
+import ctypes
 import json
 import os
 import sys
@@ -16,6 +20,7 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import platipy_amd as pa  # noqa: E402
 from platipy_amd import _lib, runtime  # noqa: E402
+from platipy_amd.registration import _mattes  # noqa: E402
 
 SIZE = (512, 512, 256)
 
@@ -33,6 +38,16 @@ def timed(fn, warmup, repeats, scrub):
         torch.cuda.synchronize()
         times.append(a.elapsed_time(b))
     return float(np.median(times)), [float(t) for t in times]
+
+
+def load_baseline(path):
+    """Another build of the library, which may predate entry points this one has: what it exports is declared, the rest is left out."""
+    dll = ctypes.CDLL(path)
+    for name, (res, argtypes) in _lib._SIGNATURES.items():
+        if hasattr(dll, name):
+            fn = getattr(dll, name)
+            fn.restype, fn.argtypes = res, argtypes
+    return dll
 
 
 def basis(t):
@@ -62,9 +77,13 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--repeats", type=int, default=7)
     ap.add_argument("--out", default=os.path.join("profiles", "bspline_bench.json"))
+    ap.add_argument("--baseline-lib", default=None, help="another build of libplatipy_hip.so whose mean-squares evaluation is timed beside this one's")
     args = ap.parse_args()
     dev = torch.device("cuda:0")
     ctx = runtime.context(dev)
+    base_ctx = None
+    if args.baseline_lib:
+        base_ctx = _lib.Context(0, torch.cuda.current_stream().cuda_stream, lib=load_baseline(args.baseline_lib))
     g = torch.Generator(device="cpu").manual_seed(1)
     fixed = torch.randn(SIZE[::-1], generator=g).to(dev)
     moving = torch.randn(SIZE[::-1], generator=g).to(dev)
@@ -75,6 +94,7 @@ def main():
     nvox = float(np.prod(SIZE))
     result = {"size": SIZE, "spacing": 1.0, "device": torch.cuda.get_device_name(0), "warmup": args.warmup, "repeats": args.repeats,
               "cases": []}
+    bins = _mattes.make_bins(30, _lib.MI_MATTES, (float(fixed.min()), float(fixed.max())), (float(moving.min()), float(moving.max())))
     for mesh in ((8, 8, 4), (32, 32, 16)):
         t = pa.bspline_transform_initializer(img, mesh)
         t.SetParameters(np.random.default_rng(2).normal(0, 2.0, t.GetNumberOfParameters()))
@@ -97,6 +117,23 @@ def main():
             case[f"metric_rate_{rate}_bytes_per_sample"] = {"compulsory": 8.0, "requested_modelled": 4.0 * 8 + 4.0 * 8,
                                                             "note": "modelled, not counted: 8 trilinear corners of each image; neighbours share cache lines"}
             case[f"metric_rate_{rate}_samples_per_us"] = nsamp / ms / 1e3
+            case[f"metric_rate_{rate}_ms_all"] = all_ms
+            if base_ctx is not None:
+                fn = lambda: base_ctx.bspline_metric(_lib.BSPLINE_MEAN_SQUARES, fixed, geom, moving, geom, geom, stride, t.coefficients, lg)  # noqa: E731
+                case[f"metric_rate_{rate}_baseline_ms"], case[f"metric_rate_{rate}_baseline_ms_all"] = timed(fn, args.warmup, args.repeats, scrub)
+            # Mattes mutual information, 30 bins: pass 1, pass 2 (on the table of pass 1's histogram) and a whole evaluation
+            margs = (fixed, geom, moving, geom, geom, stride, t.coefficients, lg, bins)
+            hist, st = ctx.bspline_mi_histogram(*margs)
+            table = _mattes.value_and_table("mattes_mi", hist, st["valid"], bins.m_bin)[1]
+
+            def evaluation():
+                h, s_ = ctx.bspline_mi_histogram(*margs)
+                return ctx.bspline_mi_gradient(*margs, _mattes.value_and_table("mattes_mi", h, s_["valid"], bins.m_bin)[1])
+
+            for key, fn in (("mi_histogram", lambda: ctx.bspline_mi_histogram(*margs)), ("mi_gradient", lambda: ctx.bspline_mi_gradient(*margs, table)),
+                            ("mi_evaluation", evaluation)):
+                case[f"{key}_rate_{rate}_ms"], case[f"{key}_rate_{rate}_ms_all"] = timed(fn, args.warmup, args.repeats, scrub)
+                case[f"{key}_rate_{rate}_over_mean_squares"] = case[f"{key}_rate_{rate}_ms"] / ms
         # torch composition of one mean-squares value + gradient on every stride-th voxel: field by einsum, grid_sample (value, and
         # the spatial gradient by autograd through the sampling positions), then index_add_ of the 64 weighted terms per sample
         def torch_metric(stride):
