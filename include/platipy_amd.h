@@ -723,6 +723,52 @@ int pp_polar_sectors_u8(pp_ctx* ctx, const uint8_t* mask, const int size[3], con
 int pp_resample_bits_u32(pp_ctx* ctx, const uint32_t* in, const pp_geom* gin, const pp_geom* gout, const double* affine_A,
                          const double* affine_t, int nbits, uint8_t* out);
 
+/* ---- inverse of a displacement field, inverse consistency, Jacobian determinant ---------- */
+/* All three: field pointers are DEVICE planar fp32 [3][Z][Y][X] on `geom`, any direction cosines.  A field of 2^32 bytes or
+ * more, or an axis longer than 65535: PP_ERR_SIZE, nothing is launched.  Reductions use integer atomics only: two calls on
+ * the same inputs return the same bits, images and statistics.  Scratch comes from the ctx workspace. */
+typedef struct pp_invert_stats {
+  int iterations;          /* iterations executed                                                        */
+  int reserved;
+  double max_error_norm;   /* max and mean over the voxels of the scaled residual norm, last executed iteration */
+  double mean_error_norm;  /* (+inf, +inf when no iteration ran)                                           */
+} pp_invert_stats;
+/* sitk.InvertDisplacementField(field, maximumNumberOfIterations, maxErrorToleranceThreshold, meanErrorToleranceThreshold,
+ * enforceBoundaryCondition) -- the operation the reference names at visualisation/visualiser.py:1536
+ * [itk::InvertDisplacementFieldImageFilter, ITK 5.3 as recalled: ITK-upstream, unverified here].  u = field, v = the
+ * estimate (initial, or 0 when NULL).  Iteration k = 1, 2, ...: c = v + u_lin(p + v) where the warped point's continuous
+ * index idx + diag(1 / spacing) Dir^T v lies in [-0.5, n - 0.5) on every axis (linear interpolation clamped at the edge
+ * cells), c = v elsewhere; r = -c; s = sqrt(sum_d (r_d / spacing_d)^2) -- physical components over index-axis spacings,
+ * no direction cosines: ITK's quirk --; M = max s, mean = sum s / N; eps = 0.75 in iteration 1 and 0.5 afterwards; where
+ * s > eps M, r *= eps M / s; v += eps r; with enforce_boundary, v = 0 on every voxel with an index 0 or n - 1.  The loop
+ * runs while k <= max_iterations and M > max_tol and mean > mean_tol, both of iteration k - 1 (+inf before the first): the
+ * iteration whose error trips a threshold still applies its own update.  One launch per iteration; the stop test runs on
+ * the device and later launches return at once.  max_iterations in 0 ... 256.  inverse_out must alias neither input.
+ * stats (HOST, may be NULL): non-NULL synchronises; otherwise the call only enqueues work. */
+int pp_invert_field_f32(pp_ctx* ctx, const float* field, const pp_geom* geom, const float* initial, int max_iterations,
+                        double max_tol, double mean_tol, int enforce_boundary, float* inverse_out, pp_invert_stats* stats);
+/* The residual of a forward / backward pair: iteration 1's c, r, s, M and mean of pp_invert_field_f32 with v = inverse
+ * and nothing updated (the same kernel arm; visualiser.py:1536 is where the reference inverts a field).  norm_out (DEVICE
+ * fp32 [Z][Y][X], may be NULL) = s.  stats (HOST, required): iterations = 1, max_error_norm = M, mean_error_norm = mean.
+ * Synchronises. */
+int pp_inverse_consistency_f32(pp_ctx* ctx, const float* field, const float* inverse, const pp_geom* geom, float* norm_out,
+                               pp_invert_stats* stats);
+typedef struct pp_jacobian_stats {
+  double min, max, mean;       /* over the mask's non-zero voxels, or every voxel; NaN when there is none */
+  int64_t count;               /* voxels taken                                                            */
+  int64_t count_nonpositive;   /* of them, det <= 0 (or NaN): where the field folds                       */
+} pp_jacobian_stats;
+/* sitk.DisplacementFieldJacobianDeterminant(field, useImageSpacing), the companion of the inversion above
+ * (visualiser.py:1536) [itk::DisplacementFieldJacobianDeterminantFilter: ITK-upstream, unverified here]:
+ * J[i][j] = 0.5 w_i (u_j(x + e_i) - u_j(x - e_i)) + delta_ij with w_i = 1 / spacing_i (use_image_spacing) or 1, a neighbour
+ * outside the buffer being the voxel itself (zero-flux Neumann: a border derivative is half the one-sided difference, an
+ * axis of length 1 contributes 0); direction cosines are not applied.  det_out (DEVICE fp32 [Z][Y][X], may be NULL when
+ * stats is given) = det J in fp32.  mask (DEVICE uint8, may be NULL) restricts the statistics, never the image.  stats
+ * (HOST, may be NULL) come from the same pass: min / max exact, mean from a 2^-24 fixed-point sum, counts exact; non-NULL
+ * synchronises, otherwise the call only enqueues work. */
+int pp_jacobian_determinant_f32(pp_ctx* ctx, const float* field, const pp_geom* geom, int use_image_spacing, const uint8_t* mask,
+                                float* det_out, pp_jacobian_stats* stats);
+
 #ifdef __cplusplus
 }
 #endif

@@ -121,6 +121,16 @@ DOSE_MAX_LABELS, DOSE_MAX_BINS, ORDER_STATS_MAX_RANKS = 64, 1 << 20, 8
 DOSE_STATS_DTYPE = np.dtype([("count", "<i8"), ("mask_sum", "<i8"), ("dose_sum", "<f8"), ("dose_min", "<f4"), ("dose_max", "<f4")])
 
 
+class InvertStats(C.Structure):      # pp_invert_stats
+    _fields_ = [("iterations", C.c_int), ("reserved", C.c_int), ("max_error_norm", C.c_double), ("mean_error_norm", C.c_double)]
+
+
+class JacobianStats(C.Structure):    # pp_jacobian_stats
+    _fields_ = [("min", C.c_double), ("max", C.c_double), ("mean", C.c_double), ("count", C.c_int64), ("count_nonpositive", C.c_int64)]
+
+
+INVERT_MAX_ITERATIONS = 256
+
 POLAR_CW, POLAR_ANY_AREA = 1, 2      # PP_POLAR_CW, PP_POLAR_ANY_AREA
 # pp_polar_slice / pp_polar_rule as numpy records (host tables of pp_polar_sectors_u8)
 POLAR_SLICE_DTYPE = np.dtype([("cy", "<f8"), ("cx", "<f8"), ("theta0", "<f8"), ("radius_min", "<f8"), ("first_rule", "<i4"), ("nrules", "<i4")])
@@ -240,6 +250,9 @@ _SIGNATURES = {
     "pp_binary_median_u8": (C.c_int, [_P, _P, C.POINTER(C.c_int), C.POINTER(C.c_int), _P]),
     "pp_polar_sectors_u8": (C.c_int, [_P, _P, C.POINTER(C.c_int), _P, _P, C.c_int, C.c_double, C.c_double, _P, _P]),
     "pp_resample_bits_u32": (C.c_int, [_P, _P, C.POINTER(Geom), C.POINTER(Geom), C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_int, _P]),
+    "pp_invert_field_f32": (C.c_int, [_P, _P, C.POINTER(Geom), _P, C.c_int, C.c_double, C.c_double, C.c_int, _P, C.POINTER(InvertStats)]),
+    "pp_inverse_consistency_f32": (C.c_int, [_P, _P, _P, C.POINTER(Geom), _P, C.POINTER(InvertStats)]),
+    "pp_jacobian_determinant_f32": (C.c_int, [_P, _P, C.POINTER(Geom), C.c_int, _P, _P, C.POINTER(JacobianStats)]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
@@ -818,6 +831,43 @@ class Context:
             raise ValueError("resample_bits: a translation needs its matrix (pass the identity)")
         self._chk_value(self.lib.pp_resample_bits_u32(self.h, ptr(src), C.byref(gin), C.byref(gout), _dn(affine_A, 9), _dn(affine_t, 3),
                                                       int(nbits), ptr(out)), "pp_resample_bits_u32")
+
+    # -- displacement-field inverse / Jacobian ----------------------------------------
+    def invert_field(self, field, geom, out, initial=None, max_iterations=10, max_tol=0.1, mean_tol=0.001, enforce_boundary=True,
+                     want_stats=False):
+        """pp_invert_field_f32: out (planar fp32 [3, Z, Y, X]) = the iterative inverse of `field` on `geom`, from `initial` or 0.
+        want_stats: -> {"iterations", "max_error_norm", "mean_error_norm"} of the last executed iteration (synchronises);
+        otherwise None and the call only enqueues work.  ValueError for what the library refuses as an argument."""
+        _check_volume("invert_field", geom.size, field=(field, 12), out=(out, 12), initial=(initial, 12))
+        st = InvertStats()
+        self._chk_value(self.lib.pp_invert_field_f32(self.h, ptr(field), C.byref(geom), ptr(initial), int(max_iterations), float(max_tol),
+                                                     float(mean_tol), int(bool(enforce_boundary)), ptr(out),
+                                                     C.byref(st) if want_stats else None), "pp_invert_field_f32")
+        if not want_stats:
+            return None
+        return {"iterations": int(st.iterations), "max_error_norm": float(st.max_error_norm), "mean_error_norm": float(st.mean_error_norm)}
+
+    def inverse_consistency(self, field, inverse, geom, norm_out=None):
+        """pp_inverse_consistency_f32 -> {"max", "mean"} of the scaled residual norm of `inverse` against `field`; norm_out (fp32
+        [Z, Y, X]) receives the norm image when given.  Synchronises."""
+        _check_volume("inverse_consistency", geom.size, field=(field, 12), inverse=(inverse, 12), norm_out=(norm_out, 4))
+        st = InvertStats()
+        self._chk_value(self.lib.pp_inverse_consistency_f32(self.h, ptr(field), ptr(inverse), C.byref(geom), ptr(norm_out), C.byref(st)),
+                        "pp_inverse_consistency_f32")
+        return {"max": float(st.max_error_norm), "mean": float(st.mean_error_norm)}
+
+    def jacobian_determinant(self, field, geom, out, use_image_spacing=True, mask=None, want_stats=False):
+        """pp_jacobian_determinant_f32: out (fp32 [Z, Y, X], or None with want_stats) = det(I + grad u).  want_stats: ->
+        {"min", "max", "mean", "count", "count_nonpositive"} over `mask` (uint8) or the whole image, from the same pass
+        (synchronises); otherwise None."""
+        _check_volume("jacobian_determinant", geom.size, field=(field, 12), out=(out, 4), mask=(mask, 1))
+        st = JacobianStats()
+        self._chk_value(self.lib.pp_jacobian_determinant_f32(self.h, ptr(field), C.byref(geom), int(bool(use_image_spacing)), ptr(mask),
+                                                             ptr(out), C.byref(st) if want_stats else None), "pp_jacobian_determinant_f32")
+        if not want_stats:
+            return None
+        return {"min": float(st.min), "max": float(st.max), "mean": float(st.mean), "count": int(st.count),
+                "count_nonpositive": int(st.count_nonpositive)}
 
     def label_contour(self, mask, size, out):
         self._chk(self.lib.pp_label_contour_u8(self.h, ptr(mask), _i3(size), ptr(out)), "pp_label_contour_u8")

@@ -964,3 +964,4 @@ int pp_compose_field_f32(pp_ctx* ctx, float* total, const float* iter, const pp_
 }  // extern "C"
 
 #include "pp_ventricle.h"   // pp_polar_sectors_u8, pp_resample_bits_u32 (uses the coordinate helpers above)
+#include "pp_field_inverse.h"   // pp_invert_field_f32, pp_inverse_consistency_f32, pp_jacobian_determinant_f32 (launch geometry above)

@@ -12,4 +12,10 @@ from .utils import (  # noqa: F401
     smooth_and_resample,
     transform_to_displacement_field,
 )
+from .field import (  # noqa: F401
+    displacement_field_jacobian_determinant,
+    inverse_consistency_error,
+    inverse_transform,
+    invert_displacement_field,
+)
 from ..label.region import connected_threshold  # noqa: E402,F401  (sitk.ConnectedThreshold: a region-growing segmentation filter)

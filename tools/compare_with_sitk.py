@@ -140,6 +140,28 @@ def main():
           "platipy_amd.registration.linear_registration on the same pair on a GPU box and compare the corner displacements "
           "(tests/test_linear.py::test_linear_registration_recovers_known_transform holds the build to < 1 mm of the known map)")
 
+    # 10. inverse of a displacement field and its Jacobian determinant on a seeded field (visualisation/visualiser.py:1536 and its
+    #     companion): the fp64 restatement the kernels are held to (tests/field_inverse_restatement.py) against SimpleITK itself
+    from tests import field_inverse_restatement as FR
+
+    fshape, fspacing = (9, 18, 33), (0.9, 0.9, 2.5)
+    u = FR.windowed_sinusoid(fshape, fspacing, seed=0)
+    U = to_sitk(u, fspacing, origin, True)
+    for n, thresholds in ((1, (0.0, 0.0)), (10, (0.0, 0.0)), (10, (0.1, 0.001))):
+        flt = sitk.InvertDisplacementFieldImageFilter()
+        flt.SetMaximumNumberOfIterations(n)
+        flt.SetMaxErrorToleranceThreshold(thresholds[0])
+        flt.SetMeanErrorToleranceThreshold(thresholds[1])
+        flt.SetEnforceBoundaryCondition(True)
+        want = np.moveaxis(sitk.GetArrayFromImage(flt.Execute(U)), -1, 0)
+        got, hist = FR.invert(u, fspacing, np.eye(3), n, thresholds[0], thresholds[1], True)
+        report(f"InvertDisplacementField, {n} it., tol {thresholds}", got, want)
+        print(f"    iterations {len(hist)}  max error norm {hist[-1]['M']:.6f} vs {flt.GetMaxErrorNorm():.6f}"
+              f"  mean {hist[-1]['mean']:.6f} vs {flt.GetMeanErrorNorm():.6f}")
+    for use_spacing in (True, False):
+        want = sitk.GetArrayFromImage(sitk.DisplacementFieldJacobianDeterminant(U, use_spacing))
+        report(f"DisplacementFieldJacobianDeterminant spacing={use_spacing}", FR.jacobian_determinant(u, fspacing, use_spacing), want)
+
     try:
         import torch
 
