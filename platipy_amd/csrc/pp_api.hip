@@ -93,10 +93,10 @@ struct pp_switch_def {
   bool numeric;   // the value must parse as an integer (else: presence is what counts)
 };
 constexpr pp_switch_def SWITCHES[] = {
-    {"PP_CC_ROWS_BLOCK", false},  {"PP_COMPOSE_BLOCK", true},  {"PP_FIR_LEGACY", false},   {"PP_FIR_MARCH_SP", true},
+    {"PP_COMPOSE_BLOCK", true},    {"PP_FIR_LEGACY", false},   {"PP_FIR_MARCH_SP", true},
     {"PP_FUSED_CUBE", true},      {"PP_FUSED_GEN", true},       {"PP_FUSED_MASK", true},     {"PP_FUSED_MIX", true},     {"PP_FUSED_NT", true},
     {"PP_FUSED_PITCH", true},     {"PP_FUSED_SUM", true},      {"PP_FUSED_TILE", true},     {"PP_FUSED_ZCHUNK", true},
-    {"PP_GAUSS3", true},          {"PP_METRIC_BLOCKS", true},  {"PP_METRIC_GRAD_ONE_LAUNCH", true}, {"PP_METRIC_LANES", true},
+    {"PP_GAUSS3", true},          {"PP_METRIC_BLOCKS", true},
     {"PP_METRIC_GRAD_PLANAR", false},
     {"PP_NO_FIXED_SAMPLES", false}, {"PP_POISON_WS", false},   {"PP_RESAMPLE_GENERIC", false}, {"PP_RG_GRID", true},
     {"PP_RG_SEG_V1", false},      {"PP_RG_TWO_SWEEP", false},  {"PP_RS_BAND", true},       {"PP_RS_ZCHUNK", true},

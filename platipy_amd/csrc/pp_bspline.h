@@ -319,7 +319,7 @@ __device__ __forceinline__ int bsp_sample(const float* __restrict__ F, const pp_
         for (int q = 0; q < 8; ++q) ag[q] = a.grad[r * N + o[q]];
         gi[r] = bsp_lerp8(ag, ux, uy, uz);
       }
-    } else if (GRAD) {   // gradient of the trilinear interpolant, per moving voxel (as k_metric_affine)
+    } else if (GRAD) {   // gradient of the trilinear interpolant, per moving voxel (as k_metric_grad)
       const float v00 = am[0] + (am[1] - am[0]) * ux, v10 = am[2] + (am[3] - am[2]) * ux;
       const float v01 = am[4] + (am[5] - am[4]) * ux, v11 = am[6] + (am[7] - am[6]) * ux;
       const float v0 = v00 + (v10 - v00) * uy, v1 = v01 + (v11 - v01) * uy;

@@ -46,63 +46,13 @@ __device__ __forceinline__ void cc_unite(int* L, int a, int b) {
   }
 }
 
-// Stage 1, rows: every voxel points at the first voxel of its x-run of equal values.  A thread walks CC_E
-// consecutive voxels; the position of the last run start at or before each thread's span comes from a max-scan over
-// the threads' last starts through LDS (NT x CC_E voxels per pass, with a carry for longer rows).
+// Stage 1, rows: every voxel points at the first voxel of its x-run of equal values.  One WAVEFRONT per row pass (rows up
+// to 512 voxels in one pass, longer ones with a carry): a lane walks CC_E consecutive voxels, the run start in force at
+// its span comes from a max-scan over the lanes' last starts by wavefront shuffles -- no LDS, no block barrier, four rows
+// per block at a time.  (A block per row kept 38 of 256 threads busy on the pipelines' ~300-voxel rows and paid twelve
+// block barriers per row.)
 // fg_only: background voxels keep their own index.
 constexpr int CC_E = 8;
-__global__ void __launch_bounds__(NT) k_cc_rows(const uint8_t* __restrict__ mask, int* __restrict__ L, pp_dims d, int fg_only) {
-  __shared__ int s[NT];
-  __shared__ int carry_s;
-  const size_t rows = (size_t)d.ny * d.nz;
-  const int span = NT * CC_E;
-  for (size_t row = blockIdx.x; row < rows; row += gridDim.x) {
-    const uint8_t* m = mask + row * d.nx;
-    int carry = 0;
-    for (int x0 = 0; x0 < d.nx; x0 += span) {
-      const int left = d.nx - x0;
-      const int nact = left >= span ? NT : (left + CC_E - 1) / CC_E;   // threads with at least one voxel
-      const int xb = x0 + (int)threadIdx.x * CC_E;
-      bool v[CC_E];
-      int last = -1;                       // last run start inside my span
-      bool prev = xb > 0 && xb <= d.nx ? m[xb - 1] != 0 : false;
-      for (int e = 0; e < CC_E; ++e) {
-        const int x = xb + e;
-        v[e] = x < d.nx ? m[x] != 0 : false;
-        if (x < d.nx && (x == 0 || v[e] != prev)) last = x;
-        prev = v[e];
-      }
-      s[threadIdx.x] = last;
-      __syncthreads();
-      for (int off = 1; off < nact; off <<= 1) {
-        const int t = (int)threadIdx.x >= off ? s[threadIdx.x - off] : -1;
-        __syncthreads();
-        if (t > s[threadIdx.x]) s[threadIdx.x] = t;
-        __syncthreads();
-      }
-      // run start in force when my span begins: the scan over the threads to my left, else the carry
-      int cur = threadIdx.x > 0 ? s[threadIdx.x - 1] : -1;
-      if (cur < 0) cur = carry;
-      prev = xb > 0 && xb <= d.nx ? m[xb - 1] != 0 : false;
-      for (int e = 0; e < CC_E; ++e) {
-        const int x = xb + e;
-        if (x >= d.nx) break;
-        if (x == 0 || v[e] != prev) cur = x;
-        prev = v[e];
-        L[row * d.nx + x] = (fg_only && !v[e]) ? (int)(row * d.nx + x) : (int)(row * d.nx + cur);
-      }
-      if ((int)threadIdx.x == nact - 1) carry_s = s[threadIdx.x] >= 0 ? s[threadIdx.x] : carry;
-      __syncthreads();
-      carry = carry_s;
-      __syncthreads();
-    }
-  }
-}
-
-// The same labelling with one WAVEFRONT per row pass (rows up to 512 voxels in one pass, longer ones with a carry): a lane
-// walks CC_E consecutive voxels, the run start in force at its span comes from a max-scan over the lanes by wavefront
-// shuffles -- no LDS, no block barrier, four rows per block at a time.  (A block per row kept 38 of 256 threads busy on the
-// pipelines' ~300-voxel rows and paid twelve block barriers per row.)
 __global__ void __launch_bounds__(NT) k_cc_rows_wave(const uint8_t* __restrict__ mask, int* __restrict__ L, pp_dims d, int fg_only) {
   const size_t rows = (size_t)d.ny * d.nz;
   const int lane = (int)threadIdx.x & 63, wib = (int)threadIdx.x >> 6;
@@ -314,13 +264,9 @@ unsigned grid_for(size_t work, unsigned cap = 16384u) {
 int cc_label(pp_ctx* ctx, const uint8_t* mask, int* L, const pp_dims& d, size_t n, int fg_only, int full = 0) {
   const dim3 g(grid_for(n)), b(NT);
   const size_t rows = (size_t)d.ny * d.nz;
-  if (pp_env("PP_CC_ROWS_BLOCK")) {   // (the block-per-row form, for A/B runs)
-    hipLaunchKernelGGL(k_cc_rows, dim3((unsigned)(rows < 65535 ? rows : 65535)), b, 0, ctx->stream, mask, L, d, fg_only);
-  } else {
-    const size_t nbr = (rows + NT / 64 - 1) / (NT / 64);
-    hipLaunchKernelGGL(k_cc_rows_wave, dim3((unsigned)(nbr < 16384 ? nbr : 16384)), b, 0, ctx->stream, mask, L, d, fg_only);
-  }
-  PP_LAUNCH_CHECK(ctx, "k_cc_rows");
+  const size_t nbr = (rows + NT / 64 - 1) / (NT / 64);
+  hipLaunchKernelGGL(k_cc_rows_wave, dim3((unsigned)(nbr < 16384 ? nbr : 16384)), b, 0, ctx->stream, mask, L, d, fg_only);
+  PP_LAUNCH_CHECK(ctx, "k_cc_rows_wave");
   if (full) hipLaunchKernelGGL(k_cc_merge<true>, g, b, 0, ctx->stream, mask, L, d, fg_only);
   else hipLaunchKernelGGL(k_cc_merge<false>, g, b, 0, ctx->stream, mask, L, d, fg_only);
   PP_LAUNCH_CHECK(ctx, "k_cc_merge");

@@ -232,8 +232,12 @@ __global__ void __launch_bounds__(NT) k_minmax_final(const float* __restrict__ p
 // grid, as itk::ImageRegistrationMethodv4's REGULAR sampling walks its virtual domain.  For a
 // sample with virtual index v:   f = trilinear(fixed,  Af v + bf),   m = trilinear(moving, Am v + bm),
 // g = gradient of the moving interpolant in moving-index units; samples whose fixed or moving
-// point leaves the buffer (or a mask) are skipped.  Accumulated in fp64:
+// point leaves the buffer (or a mask) are skipped.  Accumulated in fp64 (k_metric_grad<MODE, GI>):
+// MODE 0: mean squares, NACC = 14:
 //   [0] sum (f-m)^2   [1] count   [2..10] d/dAm[r][q] = sum -2 (f-m) g_r v_q   [11..13] d/dbm[r] = sum -2 (f-m) g_r
+// MODE 1: raw moments for the correlation metric, NACC = 42:
+//   [0] count [1] sum f [2] sum m [3] sum f^2 [4] sum m^2 [5] sum f m
+//   [6..17] sum g (d/dAm row-major 9, d/dbm 3)   [18..29] sum f g   [30..41] sum m g      (g = interpolant gradient terms)
 struct msq_args {
   double Af[9], bf[3], Am[9], bm[3];
   int vsize[3];
@@ -286,121 +290,8 @@ __device__ __forceinline__ void msq_gradient_image(const float* __restrict__ gra
   }
 }
 
-// MODE 0: mean squares, NACC = 14 (layout above).
-// MODE 1: raw moments for the correlation metric, NACC = 42:
-//   [0] count [1] sum f [2] sum m [3] sum f^2 [4] sum m^2 [5] sum f m
-//   [6..17] sum g (d/dAm row-major 9, d/dbm 3)   [18..29] sum f g   [30..41] sum m g      (g = interpolant gradient terms)
-template <int MODE>
-__global__ void __launch_bounds__(NT) k_metric_affine(const float* __restrict__ F, pp_dims df, const float* __restrict__ M,
-                                                      pp_dims dm, const uint8_t* __restrict__ fmask,
-                                                      const uint8_t* __restrict__ mmask, msq_args a,
-                                                      double* __restrict__ partials /* [grid][NACC] */,
-                                                      const float* __restrict__ fsamp /* pp_fixed_samples, or NULL */) {
-  constexpr int NACC = MODE == 0 ? 14 : 42;
-  __shared__ double red[3 * NT];
-  double acc[NACC];
-  for (int k = 0; k < NACC; ++k) acc[k] = 0.0;
-  const size_t nvirt = (size_t)a.vsize[0] * a.vsize[1] * a.vsize[2];
-  const size_t nsamp = (nvirt + a.stride - 1) / a.stride;
-  for (size_t e = (size_t)blockIdx.x * NT + threadIdx.x; e < nsamp; e += (size_t)gridDim.x * NT) {
-    const size_t lin = e * (size_t)a.stride;
-    double v[3] = {(double)(lin % a.vsize[0]), (double)((lin / a.vsize[0]) % a.vsize[1]),
-                   (double)(lin / ((size_t)a.vsize[0] * a.vsize[1]))};
-    msq_jitter(a.jit, e, v);
-    double cf[3], cm[3];
-    for (int r = 0; r < 3; ++r) {
-      cf[r] = a.Af[r * 3 + 0] * v[0] + a.Af[r * 3 + 1] * v[1] + a.Af[r * 3 + 2] * v[2] + a.bf[r];
-      cm[r] = a.Am[r * 3 + 0] * v[0] + a.Am[r * 3 + 1] * v[1] + a.Am[r * 3 + 2] * v[2] + a.bm[r];
-    }
-    int bf_[3], bm_[3];
-    float ff[3], fm[3];
-    float fval = 0.0f;
-    if (fsamp) {   // the fixed side of this sample was evaluated once for the level (same arithmetic)
-      fval = fsamp[e];
-      if (__builtin_bit_cast(unsigned, fval) == PP_FSAMP_INVALID) continue;
-      if (!msq_locate(cm, dm, bm_, fm)) continue;
-    } else {
-      if (!msq_locate(cf, df, bf_, ff) || !msq_locate(cm, dm, bm_, fm)) continue;
-      if (fmask) {
-        const int qx = (int)floor(cf[0] + 0.5), qy = (int)floor(cf[1] + 0.5), qz = (int)floor(cf[2] + 0.5);
-        if (!fmask[((size_t)qz * df.ny + qy) * df.nx + qx]) continue;
-      }
-    }
-    if (mmask) {
-      const int qx = (int)floor(cm[0] + 0.5), qy = (int)floor(cm[1] + 0.5), qz = (int)floor(cm[2] + 0.5);
-      if (!mmask[((size_t)qz * dm.ny + qy) * dm.nx + qx]) continue;
-    }
-    if (!fsamp) fval = pp_trilinear(F, df.nx, df.ny, df.nz, bf_[0], ff[0], bf_[1], ff[1], bf_[2], ff[2]);
-    int x0, x1, y0, y1, z0, z1;
-    float wx, wy, wz;
-    pp_axis_setup(bm_[0], fm[0], dm.nx, x0, x1, wx);
-    pp_axis_setup(bm_[1], fm[1], dm.ny, y0, y1, wy);
-    pp_axis_setup(bm_[2], fm[2], dm.nz, z0, z1, wz);
-    const size_t sy = dm.nx, sz = (size_t)dm.nx * dm.ny;
-    const float a000 = M[z0 * sz + y0 * sy + x0], a100 = M[z0 * sz + y0 * sy + x1];
-    const float a010 = M[z0 * sz + y1 * sy + x0], a110 = M[z0 * sz + y1 * sy + x1];
-    const float a001 = M[z1 * sz + y0 * sy + x0], a101 = M[z1 * sz + y0 * sy + x1];
-    const float a011 = M[z1 * sz + y1 * sy + x0], a111 = M[z1 * sz + y1 * sy + x1];
-    const float v00 = a000 + (a100 - a000) * wx, v10 = a010 + (a110 - a010) * wx;
-    const float v01 = a001 + (a101 - a001) * wx, v11 = a011 + (a111 - a011) * wx;
-    const float v0 = v00 + (v10 - v00) * wy, v1 = v01 + (v11 - v01) * wy;
-    const float m = v0 + (v1 - v0) * wz;
-    // gradient of the trilinear interpolant, per moving voxel
-    const float gx0 = (a100 - a000) + ((a110 - a010) - (a100 - a000)) * wy;
-    const float gx1 = (a101 - a001) + ((a111 - a011) - (a101 - a001)) * wy;
-    float gx = gx0 + (gx1 - gx0) * wz;
-    float gy = (v10 - v00) + ((v11 - v01) - (v10 - v00)) * wz;
-    float gz = v1 - v0;
-    if (a.grad) {   // (uniform) ITK's filtered gradient image instead of the interpolant's derivative
-      float gi[3];
-      msq_gradient_image(a.grad, dm, x0, x1, y0, y1, z0, z1, wx, wy, wz, gi);
-      gx = gi[0]; gy = gi[1]; gz = gi[2];
-    }
-    if (MODE == 0) {
-      const double diff = (double)fval - (double)m;
-      acc[0] += diff * diff;
-      acc[1] += 1.0;
-      const double s = -2.0 * diff;
-      const double g[3] = {s * gx, s * gy, s * gz};
-      for (int r = 0; r < 3; ++r) {
-        acc[2 + r * 3 + 0] += g[r] * v[0];
-        acc[2 + r * 3 + 1] += g[r] * v[1];
-        acc[2 + r * 3 + 2] += g[r] * v[2];
-        acc[11 + r] += g[r];
-      }
-    } else {
-      const double fd = fval, md = m;
-      acc[0] += 1.0;
-      acc[1] += fd;
-      acc[2] += md;
-      acc[3] += fd * fd;
-      acc[4] += md * md;
-      acc[5] += fd * md;
-      const double g[3] = {gx, gy, gz};
-      for (int r = 0; r < 3; ++r)
-        for (int q = 0; q < 4; ++q) {
-          const double t = g[r] * (q < 3 ? v[q] : 1.0);
-          const int slot = q < 3 ? r * 3 + q : 9 + r;
-          acc[6 + slot] += t;
-          acc[18 + slot] += fd * t;
-          acc[30 + slot] += md * t;
-        }
-    }
-  }
-  for (int k = 0; k < NACC; k += 3) {
-    double p = acc[k], q = k + 1 < NACC ? acc[k + 1] : 0.0, r = k + 2 < NACC ? acc[k + 2] : 0.0;
-    pp_block_sum3<NT>(p, q, r, red);
-    if (threadIdx.x == 0) {
-      partials[(size_t)blockIdx.x * NACC + k] = p;
-      if (k + 1 < NACC) partials[(size_t)blockIdx.x * NACC + k + 1] = q;
-      if (k + 2 < NACC) partials[(size_t)blockIdx.x * NACC + k + 2] = r;
-    }
-    __syncthreads();
-  }
-}
-
-// Fold [count][14] partial rows into 14 sums with one tree (8 barrier steps for all fields at once); launched
-// with one block per group of 14 fields (blockIdx.x selects the group of a wider row).
+// Fold [count][14] partial rows into 14 sums with one tree (8 barrier steps for all fields at once).  Its one caller,
+// pp_mi_gradient_f32, launches one block with row == 14 (a wider row would take one block per group of 14 fields).
 __global__ void __launch_bounds__(NT) k_sum14_final(const double* __restrict__ partials, int count, int row, double* result,
                                                     int to_mailbox, unsigned long long seq) {
   __shared__ double red[NT * 14];
@@ -429,9 +320,9 @@ __global__ void __launch_bounds__(NT) k_sum14_final(const double* __restrict__ p
 // The golden-section line search of ITK's GradientDescentLineSearchOptimizerv4 needs ~13 metric VALUES per
 // optimiser iteration, each depending on the previous comparison; one launch + one read-back per value is pure
 // latency (the sample lattice is 16 K .. 1 M points).  The host speculates the next few levels of the search
-// tree and evaluates all of their learning rates at once: blockIdx.y = candidate.  The last block of a candidate to
-// finish (device ticket per candidate) folds that candidate's per-block partial sums with a fixed tree, so a candidate's value does not depend on
-// which other candidates ride in the launch.  (ctx->ticket holds 16 counters 128 bytes apart; a chunk uses the one at chunk * TICKET_STRIDE.)
+// tree and evaluates all of their learning rates at once (k_metric_values_lanes, below).  The last block to finish
+// (device ticket) folds the per-block partial sums with a fixed tree, so a candidate's value does not depend on
+// which other candidates ride in the launch.
 constexpr int PP_MAX_CAND = 16;
 constexpr unsigned TICKET_STRIDE = 32;   // counters sit 128 bytes apart (ctx->ticket holds 16 of them)
 struct mval_args {
@@ -478,187 +369,22 @@ __device__ __forceinline__ float msq_trilinear_pairs(const float* __restrict__ i
   return v0 + (v1 - v0) * wz;
 }
 
-// MODE 0: [sum (f-m)^2, count].  MODE 1: [count, sum f, sum m, sum f^2, sum m^2, sum f m].
-// One thread walks its samples and, per sample, ALL candidates of its chunk (CH per blockIdx.y): the lattice is
-// sparse in the full-resolution images (every gather is its own cache line, so an evaluation is HBM traffic, not
-// arithmetic), the candidates of a line search land within a voxel or two of each other, and probing them
-// back-to-back turns 15 of 16 candidates' gathers into L1/L2 hits; the fixed sample is fetched once.
-template <int MODE, int CH>
-__global__ void __launch_bounds__(NT) k_metric_values(const float* __restrict__ F, pp_dims df, const float* __restrict__ M, pp_dims dm,
-                                                      const uint8_t* __restrict__ fmask, const uint8_t* __restrict__ mmask, mval_args a,
-                                                      int ncand, double* partials /* [chunk][grid.x][CH*NV] */,
-                                                      unsigned* __restrict__ ticket, void* mailbox /* host mailbox: chunk = writer */,
-                                                      unsigned long long seq, const float* __restrict__ fsamp /* or NULL */) {
-  constexpr int NV = MODE == 0 ? 2 : 6;
-  constexpr int ROW = CH * NV;
-  __shared__ double red[CH * (MODE == 0 ? 2 : 6) * NT];   // 64 KB / 48 KB: every accumulator of every thread
-  __shared__ int is_last;
-  const int c0 = blockIdx.y * CH;
-  const int nc = ncand - c0 < CH ? ncand - c0 : CH;
-  double acc[ROW];
-  for (int k = 0; k < ROW; ++k) acc[k] = 0.0;
-  const size_t nvirt = (size_t)a.vsize[0] * a.vsize[1] * a.vsize[2];
-  const size_t nsamp = (nvirt + a.stride - 1) / a.stride;
-  for (size_t e = (size_t)blockIdx.x * NT + threadIdx.x; e < nsamp; e += (size_t)gridDim.x * NT) {
-    const size_t lin = e * (size_t)a.stride;
-    double v[3] = {(double)(lin % a.vsize[0]), (double)((lin / a.vsize[0]) % a.vsize[1]),
-                   (double)(lin / ((size_t)a.vsize[0] * a.vsize[1]))};
-    msq_jitter(a.jit, e, v);
-    double fd;
-    if (fsamp) {   // the fixed side of this sample was evaluated once for the level: a coalesced 4-byte read instead of four
-                   // sparse cache lines per sample (at shrink 4 a probe dragged a quarter of the fixed image through HBM)
-      const float fv = fsamp[e];
-      if (__builtin_bit_cast(unsigned, fv) == PP_FSAMP_INVALID) continue;
-      fd = fv;
-    } else {
-      double cf[3];
-      for (int r = 0; r < 3; ++r) cf[r] = a.Af[r * 3 + 0] * v[0] + a.Af[r * 3 + 1] * v[1] + a.Af[r * 3 + 2] * v[2] + a.bf[r];
-      int bf_[3];
-      float ff[3];
-      if (!msq_locate(cf, df, bf_, ff)) continue;
-      if (fmask) {
-        const int qx = (int)floor(cf[0] + 0.5), qy = (int)floor(cf[1] + 0.5), qz = (int)floor(cf[2] + 0.5);
-        if (!fmask[((size_t)qz * df.ny + qy) * df.nx + qx]) continue;
-      }
-      fd = msq_trilinear_pairs(F, df.nx, df.ny, df.nz, bf_[0], ff[0], bf_[1], ff[1], bf_[2], ff[2]);
-    }
-    if constexpr (CH >= 16) {
-    // Straight-line over the candidates: every candidate forms a valid (clamped) address and gathers unconditionally, and
-    // "inside / masked" only selects what is accumulated -- so a group of four candidates has no branches and the gathers of the
-    // next candidates are in flight while this one is interpolated (a thread's candidates used to be a serial chain of
-    // dependent cache misses).  Adding 0.0 for a rejected candidate leaves the sums bit-identical.
-#pragma unroll
-    for (int j0 = 0; j0 < CH; j0 += 4) {
-    if (j0 < nc) {   // (block-uniform: whole groups of four beyond the batch are skipped; inside a group no branches)
-#pragma unroll
-    for (int j = j0; j < j0 + 4; ++j) {
-      double cm[3];
-      for (int r = 0; r < 3; ++r)
-        cm[r] = a.Am[c0 + j][r * 3 + 0] * v[0] + a.Am[c0 + j][r * 3 + 1] * v[1] + a.Am[c0 + j][r * 3 + 2] * v[2] + a.bm[c0 + j][r];
-      bool ok = (j < nc) & (cm[0] >= -0.5) & (cm[0] < dm.nx - 0.5) & (cm[1] >= -0.5) & (cm[1] < dm.ny - 0.5) & (cm[2] >= -0.5) &
-                (cm[2] < dm.nz - 0.5);
-      int bm_[3];
-      float fm[3];
-      for (int r = 0; r < 3; ++r) {
-        const double cc = ok ? cm[r] : 0.0;
-        const double fl = floor(cc);
-        bm_[r] = (int)fl;
-        fm[r] = (float)(cc - fl);
-      }
-      if (mmask) {   // (uniform)
-        const int qx = ok ? (int)floor(cm[0] + 0.5) : 0, qy = ok ? (int)floor(cm[1] + 0.5) : 0, qz = ok ? (int)floor(cm[2] + 0.5) : 0;
-        ok = ok & (mmask[((size_t)qz * dm.ny + qy) * dm.nx + qx] != 0);
-      }
-      const double md = dm.nx >= 2 ? (double)pp_trilinear_pairs(M, dm.nx, dm.ny, dm.nz, bm_[0], fm[0], bm_[1], fm[1], bm_[2], fm[2])
-                                   : (double)msq_trilinear_pairs(M, dm.nx, dm.ny, dm.nz, bm_[0], fm[0], bm_[1], fm[1], bm_[2], fm[2]);
-      if (MODE == 0) {
-        const double diff = fd - md;
-        acc[j * NV + 0] += ok ? diff * diff : 0.0;
-        acc[j * NV + 1] += ok ? 1.0 : 0.0;
-      } else {
-        acc[j * NV + 0] += ok ? 1.0 : 0.0;
-        acc[j * NV + 1] += ok ? fd : 0.0;
-        acc[j * NV + 2] += ok ? md : 0.0;
-        acc[j * NV + 3] += ok ? fd * fd : 0.0;
-        acc[j * NV + 4] += ok ? md * md : 0.0;
-        acc[j * NV + 5] += ok ? fd * md : 0.0;
-      }
-    }
-    }
-    }
-    } else {   // few candidates per thread: the branchy form measured faster (tools/bench_metric.py)
-#pragma unroll
-    for (int j = 0; j < CH; ++j) {
-      double cm[3];
-      for (int r = 0; r < 3; ++r)
-        cm[r] = a.Am[c0 + j][r * 3 + 0] * v[0] + a.Am[c0 + j][r * 3 + 1] * v[1] + a.Am[c0 + j][r * 3 + 2] * v[2] + a.bm[c0 + j][r];
-      int bm_[3] = {0, 0, 0};
-      float fm[3] = {0.0f, 0.0f, 0.0f};
-      bool ok = j < nc && msq_locate(cm, dm, bm_, fm);
-      if (ok && mmask) {
-        const int qx = (int)floor(cm[0] + 0.5), qy = (int)floor(cm[1] + 0.5), qz = (int)floor(cm[2] + 0.5);
-        ok = mmask[((size_t)qz * dm.ny + qy) * dm.nx + qx] != 0;
-      }
-      if (ok) {
-        const double md = msq_trilinear_pairs(M, dm.nx, dm.ny, dm.nz, bm_[0], fm[0], bm_[1], fm[1], bm_[2], fm[2]);
-        if (MODE == 0) {
-          const double diff = fd - md;
-          acc[j * NV + 0] += diff * diff;
-          acc[j * NV + 1] += 1.0;
-        } else {
-          acc[j * NV + 0] += 1.0;
-          acc[j * NV + 1] += fd;
-          acc[j * NV + 2] += md;
-          acc[j * NV + 3] += fd * fd;
-          acc[j * NV + 4] += md * md;
-          acc[j * NV + 5] += fd * md;
-        }
-      }
-    }
-    }
-  }
-  // one wide tree for all ROW accumulators (8 barrier rounds instead of 8 per triple): red[f][thread]
-  double* mine = partials + ((size_t)blockIdx.y * gridDim.x + blockIdx.x) * ROW;
-#pragma unroll
-  for (int k = 0; k < ROW; ++k) red[k * NT + threadIdx.x] = acc[k];
-  __syncthreads();
-  for (int st = NT / 2; st > 0; st >>= 1) {
-    if ((int)threadIdx.x < st) {
-#pragma unroll
-      for (int k = 0; k < ROW; ++k) red[k * NT + threadIdx.x] += red[k * NT + threadIdx.x + st];
-    }
-    __syncthreads();
-  }
-  if ((int)threadIdx.x < ROW) {
-    // agent-scope atomic store / load for the rows (below): they cross XCDs, each behind its own L2, inside one launch
-    __hip_atomic_store(mine + threadIdx.x, red[threadIdx.x * NT], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    __threadfence();   // each writer publishes its own store before the block takes its ticket
-  }
-  __syncthreads();
-  // the last block of this chunk to arrive folds the chunk's rows (fixed tree, independent of arrival order)
-  if (threadIdx.x == 0) {
-    const unsigned t = atomicAdd(ticket + blockIdx.y * TICKET_STRIDE, 1u);   // (one 128-byte line per chunk's counter)
-    is_last = t == gridDim.x - 1u;
-  }
-  __syncthreads();
-  if (!is_last) return;
-  __threadfence();
-  // Every column of the chunk's rows at once: thread (part, col) adds rows part, part + NPARTS, ... of its column (a
-  // coalesced read per row), then one thread per column adds the NPARTS partial sums in order.  Fixed tree, independent
-  // of the arrival order; one barrier instead of a block-wide tree per three columns.
-  const double* rows = partials + (size_t)blockIdx.y * gridDim.x * ROW;
-  constexpr int NPARTS = NT / ROW;
-  {
-    const int col = (int)threadIdx.x % ROW, part = (int)threadIdx.x / ROW;
-    double p = 0.0;
-    if (part < NPARTS)
-      for (unsigned i = (unsigned)part; i < gridDim.x; i += NPARTS)
-        p += __hip_atomic_load(rows + (size_t)i * ROW + col, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    __syncthreads();   // (red still holds the block's own tree)
-    if (part < NPARTS) red[part * ROW + col] = p;
-    __syncthreads();
-    if ((int)threadIdx.x < nc * NV) {
-      double tot = 0.0;
-      for (int q = 0; q < NPARTS; ++q) tot += red[q * ROW + threadIdx.x];
-      pp_mail_post(pp_mail_slot(mailbox, (int)blockIdx.y) + threadIdx.x, tot, seq);   // entry = local candidate * NV + field
-    }
-  }
-  if (threadIdx.x == 0) atomicExch(ticket + blockIdx.y * TICKET_STRIDE, 0u);   // (where the increments go, not a cached plain store)
-}
-
-// ---- line-search evaluations, second generation: a candidate is a LANE ---------------------------------------
-// k_metric_values walks a thread over its samples and, per sample, over the candidates: on the sparse lattices of the
-// pipelines (every 8th voxel of the full-resolution moving image along x) the 64 lanes of a gather then address 16-64
-// different cache lines, and the kernel runs at the vector cache's line-lookup rate (measured: 75 us for 16 candidates on
-// 524 K samples, ~64 clocks per gather instruction).  Here lane = 16 * slot + candidate: a wavefront holds FOUR
-// consecutive samples x 16 candidates; the four samples sit in neighbouring 32-byte sectors and, once the search bracket has
-// shrunk, a sample's candidates within a voxel or two of each other, so a gather instruction touches a handful of lines; a thread keeps NV
-// accumulators instead of 16 * NV (no 64 KB reduction tile: the block is bound by registers, not LDS), and a candidate's
-// samples are spread over 16 x as many threads (shorter dependent chains on the small lattices).
+// ---- the probe kernel: a candidate is a LANE -----------------------------------------------------------------
+// The lattices of the pipelines are sparse (every 8th voxel of the full-resolution moving image along x): a gather whose
+// 64 lanes hold 64 different samples addresses 16-64 different cache lines and runs at the vector cache's line-lookup
+// rate (measured, with a thread looping over the candidates of each of its samples: 75 us for 16 candidates on 524 K
+// samples, ~64 clocks per gather instruction).  Here lane = 16 * slot + candidate: a wavefront holds FOUR consecutive
+// samples x 16 candidates; the four samples sit in neighbouring 32-byte sectors and, once the search bracket has shrunk,
+// a sample's candidates within a voxel or two of each other, so a gather instruction touches a handful of lines.  A
+// thread keeps NV accumulators, so the block's reduction needs no LDS tile of every thread's sums (the block is bound
+// by registers, not LDS), and a candidate's samples are spread over the threads of 16 sample slots a block (short
+// dependent chains on the small lattices).
 // Sum order of a candidate: a thread adds its samples e0 + slot, e0 + 16 + slot, ... in increasing order; the four slots
-// of a wavefront combine as (s0 + s1) + (s2 + s3), the four wavefronts as (w0 + w1) + (w2 + w3); the last block to finish folds the
-// blocks' rows with the fixed tree of k_metric_values.  The layout does not depend on the number of candidates, so a
-// candidate's value does not depend on its companions.
+// of a wavefront combine as (s0 + s1) + (s2 + s3), the four wavefronts as (w0 + w1) + (w2 + w3).  The last block to finish
+// folds the blocks' rows: thread (part, col), part < NPARTS = NT / ROW, adds rows part, part + NPARTS, ... of column col in
+// increasing order (a coalesced read per row), then one thread per column adds the NPARTS partial sums in order.  A fixed
+// tree, independent of the arrival order; the layout does not depend on the number of candidates, so a candidate's
+// value does not depend on its companions.
 // pp_trilinear_pairs with 32-bit offsets built from 24-bit multiplies (full rate; a 64-bit offset costs four quarter-rate
 // multiplies per row pair), split into "request the four row pairs" and "interpolate" so that a caller can have the pairs of
 // several samples in flight before it touches the first.  Caller guarantees ny * nz < 2^24, nx < 2^24, nx >= 2 and fewer
@@ -701,10 +427,7 @@ template <bool B> struct mv_flag { static constexpr bool value = B; };
 constexpr int MV_CL = 16;              // lanes per sample
 constexpr int MV_SLOTS = NT / MV_CL;   // samples a block handles side by side
 template <int MODE>
-#ifndef PP_MV_WAVES
-#define PP_MV_WAVES 1
-#endif
-__global__ void __launch_bounds__(NT, PP_MV_WAVES) k_metric_values_lanes(const float* __restrict__ F, pp_dims df, const float* __restrict__ M, pp_dims dm,
+__global__ void __launch_bounds__(NT, 1) k_metric_values_lanes(const float* __restrict__ F, pp_dims df, const float* __restrict__ M, pp_dims dm,
                                                             const uint8_t* __restrict__ fmask, const uint8_t* __restrict__ mmask,
                                                             mval_args a, int ncand, int spt /* samples per thread */,
                                                             double* partials /* [grid.x][16 * NV] */, unsigned* __restrict__ ticket,
@@ -944,11 +667,11 @@ __global__ void __launch_bounds__(NT, PP_MV_WAVES) k_metric_values_lanes(const f
 }
 
 
-// ---- metric value + gradient, second generation: one launch ---------------------------------------------------
-// k_metric_affine + k_sum14_final with the lessons of the probe kernel: a thread's samples go four (two for the 42
-// correlation sums) at a time with every corner request issued before the first is used, the block folds through wavefront shuffles
-// instead of forty barrier rounds, and the last block to finish (two-level ticket, fence-free rows) folds the rows and
-// posts the sums itself: no second launch.  Per-sample terms and accumulators are those of k_metric_affine; a thread adds
+// ---- metric value + gradient: one launch ----------------------------------------------------------------------
+// Built like the probe kernel: a thread's samples go four (two for the 42 correlation sums) at a time with every
+// corner request issued before the first is used, the block folds through wavefront shuffles instead of barrier rounds
+// per accumulator, and the last block to finish (two-level ticket, fence-free rows) folds the rows and posts the sums
+// itself: no second launch.  Per-sample terms and accumulators are the layouts above msq_args; a thread adds
 // its samples in increasing order, lanes combine by mg_wave_sum16's fixed tree, wavefronts as (w0 + w1) + (w2 + w3),
 // block rows by the fixed interleaved fold of the probe kernel.
 // Sum of sixteen per-lane doubles over the 64 lanes of a wavefront by "transpose and add": at xor distance 32 a lane keeps
@@ -1651,45 +1374,22 @@ static int metric_affine(pp_ctx* ctx, int mode, const float* fixed, const int fs
   const float* fsamp = nullptr;
   rc = pp_fixed_samples(ctx, fixed, fsize, Af, bf, vsize, stride, fixed_mask, &fsamp);
   if (rc) return rc;
-  const char* one_env = pp_env("PP_METRIC_GRAD_ONE_LAUNCH");   // (0: k_metric_affine + k_sum14_final, for A/B runs and the equality test)
-  if (!one_env || atoi(one_env) != 0) {
-    unsigned* ticket = nullptr;
-    rc = pp_ticket(ctx, &ticket);
-    if (rc) return rc;
-    char* mail1 = nullptr;
-    unsigned long long seq1 = 0;
-    rc = pp_mailbox(ctx, &mail1, &seq1);
-    if (rc) return rc;
-#define PP_MG_GO(MODEV, GIV)                                                                                                              \
-  hipLaunchKernelGGL((k_metric_grad<MODEV, GIV>), dim3(nb), dim3(NT), 0, ctx->stream, fixed, df, moving, dm, fixed_mask, moving_mask, a, \
-                     partials, ticket, mail1, seq1, fsamp)
-    if (a.grad4) { if (mode == 0) PP_MG_GO(0, 2); else PP_MG_GO(1, 2); }
-    else if (a.grad) { if (mode == 0) PP_MG_GO(0, 1); else PP_MG_GO(1, 1); }
-    else { if (mode == 0) PP_MG_GO(0, 0); else PP_MG_GO(1, 0); }
-#undef PP_MG_GO
-    PP_LAUNCH_CHECK(ctx, "k_metric_grad");
-    return pp_mail_take(ctx, 0, nacc, seq1, result);
-  }
-  if (mode == 0)
-    hipLaunchKernelGGL((k_metric_affine<0>), dim3(nb), dim3(NT), 0, ctx->stream, fixed, df, moving, dm, fixed_mask, moving_mask, a, partials,
-                       fsamp);
-  else
-    hipLaunchKernelGGL((k_metric_affine<1>), dim3(nb), dim3(NT), 0, ctx->stream, fixed, df, moving, dm, fixed_mask, moving_mask, a, partials,
-                       fsamp);
-  PP_LAUNCH_CHECK(ctx, "k_metric_affine");
+  unsigned* ticket = nullptr;
+  rc = pp_ticket(ctx, &ticket);
+  if (rc) return rc;
   char* mail = nullptr;
   unsigned long long seq = 0;
   rc = pp_mailbox(ctx, &mail, &seq);
   if (rc) return rc;
-  const int nfold = (nacc + 13) / 14;
-  hipLaunchKernelGGL(k_sum14_final, dim3(nfold), dim3(NT), 0, ctx->stream, (const double*)partials, (int)nb, nacc,
-                     reinterpret_cast<double*>(mail), 1, seq);
-  PP_LAUNCH_CHECK(ctx, "k_sum14_final");
-  for (int b = 0; b < nfold; ++b) {
-    rc = pp_mail_take(ctx, b, nacc - 14 * b < 14 ? nacc - 14 * b : 14, seq, result + 14 * b);
-    if (rc) return rc;
-  }
-  return PP_OK;
+#define PP_MG_GO(MODEV, GIV)                                                                                                              \
+  hipLaunchKernelGGL((k_metric_grad<MODEV, GIV>), dim3(nb), dim3(NT), 0, ctx->stream, fixed, df, moving, dm, fixed_mask, moving_mask, a, \
+                     partials, ticket, mail, seq, fsamp)
+  if (a.grad4) { if (mode == 0) PP_MG_GO(0, 2); else PP_MG_GO(1, 2); }
+  else if (a.grad) { if (mode == 0) PP_MG_GO(0, 1); else PP_MG_GO(1, 1); }
+  else { if (mode == 0) PP_MG_GO(0, 0); else PP_MG_GO(1, 0); }
+#undef PP_MG_GO
+  PP_LAUNCH_CHECK(ctx, "k_metric_grad");
+  return pp_mail_take(ctx, 0, nacc, seq, result);
 }
 
 int pp_meansq_affine_f32(pp_ctx* ctx, const float* fixed, const int fsize[3], const float* moving, const int msize[3],
@@ -1731,67 +1431,16 @@ int pp_metric_values_affine_f32(pp_ctx* ctx, int metric, const float* fixed, con
     if (jrc) return jrc;
   }
   const pp_dims df{fsize[0], fsize[1], fsize[2]}, dm{msize[0], msize[1], msize[2]};
-  // Candidates per thread: 16 on big lattices (HBM/L2-bound: the candidates of a sample share cache lines; the straight-line
-  // form of the kernel keeps several candidates' gathers in flight), 4 for batches of up to four and on small lattices
-  // (latency-bound: spread the candidates over blocks).
-  const char* lanes_env = pp_env("PP_METRIC_LANES");   // (0: the candidate-loop kernels, for A/B runs and the equality test)
-  if (!lanes_env || atoi(lanes_env) != 0) {
-    // Blocks: the small lattices are bound by the latency of one probe (a block's dependent gather rounds, then one ticket
-    // atomic per block, ~12 ns each, serialised), the large ones by throughput.  The cap depends on the lattice only.
-    unsigned nb_cap = nsamp < 20000 ? 128u : 1024u;   // (tools/r4/run16.sh: 128 x 128 x 64 lattice 24.2 / 15.4 / 11.3 / 11.9 / 13.7 ms per level at 256 .. 4096)
-    if (const char* e = pp_env("PP_METRIC_BLOCKS")) nb_cap = (unsigned)atoi(e) > 0 ? (unsigned)atoi(e) : nb_cap;
-    size_t spt = (nsamp + (size_t)MV_SLOTS * nb_cap - 1) / ((size_t)MV_SLOTS * nb_cap);
-    spt = (spt + 3) / 4 * 4;
-    PP_REQUIRE(ctx, spt < ((size_t)1 << 30), "metric values: sampling lattice too large");
-    const unsigned nb = (unsigned)((nsamp + (size_t)MV_SLOTS * spt - 1) / ((size_t)MV_SLOTS * spt));
-    const int nv = metric == 0 ? 2 : 6, cpw = metric == 0 ? 16 : 8;
-    int rc = pp_reserve(ctx, pp_align_up((size_t)nb * MV_CL * nv * sizeof(double), 256));
-    if (rc) return rc;
-    unsigned* ticket = nullptr;
-    rc = pp_ticket(ctx, &ticket);
-    if (rc) return rc;
-    double* partials = reinterpret_cast<double*>(ctx->ws);
-    char* mail = nullptr;
-    unsigned long long seq = 0;
-    rc = pp_mailbox(ctx, &mail, &seq);
-    if (rc) return rc;
-    const float* fsamp = nullptr;
-    rc = pp_fixed_samples(ctx, fixed, fsize, Af, bf, vsize, stride, fixed_mask, &fsamp);
-    if (rc) return rc;
-    if (metric == 0)
-      hipLaunchKernelGGL((k_metric_values_lanes<0>), dim3(nb), dim3(NT), 0, ctx->stream, fixed, df, moving, dm, fixed_mask, moving_mask, a,
-                         ncand, (int)spt, partials, ticket, mail, seq, fsamp);
-    else
-      hipLaunchKernelGGL((k_metric_values_lanes<1>), dim3(nb), dim3(NT), 0, ctx->stream, fixed, df, moving, dm, fixed_mask, moving_mask, a,
-                         ncand, (int)spt, partials, ticket, mail, seq, fsamp);
-    PP_LAUNCH_CHECK(ctx, "k_metric_values_lanes");
-    memset(result, 0, (size_t)ncand * 6 * sizeof(double));
-    for (int w = 0; w * cpw < ncand; ++w) {
-      const int k = ncand - w * cpw < cpw ? ncand - w * cpw : cpw;
-      double vals[PP_MAIL_ENTRIES];
-      rc = pp_mail_take(ctx, w, k * nv, seq, vals);
-      if (rc) return rc;
-      for (int j = 0; j < k; ++j)
-        for (int f = 0; f < nv; ++f) result[((size_t)w * cpw + j) * 6 + f] = vals[j * nv + f];
-    }
-    return PP_OK;
-  }
-  constexpr int CH0 = 16, CH0S = 4, CH1 = 4;
-  const bool small = metric == 0 && nsamp < 150000;
-  const int ch = metric == 0 ? (small || ncand <= 4 ? CH0S : CH0) : CH1, nv = metric == 0 ? 2 : 6;
-  const int nchunk = (ncand + ch - 1) / ch;
-  PP_REQUIRE(ctx, nchunk <= PP_MAIL_WRITERS, "metric values: more chunks than mailbox writers");
-  // Blocks per chunk: one sample per thread up to ~512 blocks in the whole launch (512 on big lattices, where 16 candidates
-  // are one chunk; 128 on small ones, where they are four).  Measured on MI355X (profiles/round3_metric_probe_latency.txt):
-  // beyond that a probe gets SLOWER with more blocks -- 1024 blocks of two samples per thread cost 76 / 150 us (1 / 16
-  // candidates, 128 x 128 x 64 lattice), 512 blocks of four 54 / 125 us; the 64 x 64 x 32 lattice with 16 candidates 78 -> 57 us
-  // at 128 blocks per chunk.  (Not the ticket: a two-level ticket changed nothing.)  The cap depends on the lattice only, so
-  // a candidate's partial sums do not depend on how many companions ride in the launch.  PP_METRIC_BLOCKS overrides it.
-  unsigned nb_cap = (metric == 0 && small) || metric != 0 ? 128u : 512u;
-  if (const char* e = pp_env("PP_METRIC_BLOCKS")) nb_cap = (unsigned)atoi(e);
-  const unsigned nb = grid_for(nsamp, nb_cap);
-  const size_t row = (size_t)ch * nv;
-  int rc = pp_reserve(ctx, pp_align_up((size_t)nb * nchunk * row * sizeof(double), 256));
+  // Blocks: the small lattices are bound by the latency of one probe (a block's dependent gather rounds, then one ticket
+  // atomic per block, ~12 ns each, serialised), the large ones by throughput.  The cap depends on the lattice only.
+  unsigned nb_cap = nsamp < 20000 ? 128u : 1024u;   // (tools/r4/run16.sh: 128 x 128 x 64 lattice 24.2 / 15.4 / 11.3 / 11.9 / 13.7 ms per level at 256 .. 4096)
+  if (const char* e = pp_env("PP_METRIC_BLOCKS")) nb_cap = (unsigned)atoi(e) > 0 ? (unsigned)atoi(e) : nb_cap;
+  size_t spt = (nsamp + (size_t)MV_SLOTS * nb_cap - 1) / ((size_t)MV_SLOTS * nb_cap);
+  spt = (spt + 3) / 4 * 4;
+  PP_REQUIRE(ctx, spt < ((size_t)1 << 30), "metric values: sampling lattice too large");
+  const unsigned nb = (unsigned)((nsamp + (size_t)MV_SLOTS * spt - 1) / ((size_t)MV_SLOTS * spt));
+  const int nv = metric == 0 ? 2 : 6, cpw = metric == 0 ? 16 : 8;
+  int rc = pp_reserve(ctx, pp_align_up((size_t)nb * MV_CL * nv * sizeof(double), 256));
   if (rc) return rc;
   unsigned* ticket = nullptr;
   rc = pp_ticket(ctx, &ticket);
@@ -1804,24 +1453,21 @@ int pp_metric_values_affine_f32(pp_ctx* ctx, int metric, const float* fixed, con
   const float* fsamp = nullptr;
   rc = pp_fixed_samples(ctx, fixed, fsize, Af, bf, vsize, stride, fixed_mask, &fsamp);
   if (rc) return rc;
-  if (metric == 0 && ch == CH0S)
-    hipLaunchKernelGGL((k_metric_values<0, CH0S>), dim3(nb, nchunk), dim3(NT), 0, ctx->stream, fixed, df, moving, dm, fixed_mask,
-                       moving_mask, a, ncand, partials, ticket, mail, seq, fsamp);
-  else if (metric == 0)
-    hipLaunchKernelGGL((k_metric_values<0, CH0>), dim3(nb, nchunk), dim3(NT), 0, ctx->stream, fixed, df, moving, dm, fixed_mask,
-                       moving_mask, a, ncand, partials, ticket, mail, seq, fsamp);
+  if (metric == 0)
+    hipLaunchKernelGGL((k_metric_values_lanes<0>), dim3(nb), dim3(NT), 0, ctx->stream, fixed, df, moving, dm, fixed_mask, moving_mask, a,
+                       ncand, (int)spt, partials, ticket, mail, seq, fsamp);
   else
-    hipLaunchKernelGGL((k_metric_values<1, CH1>), dim3(nb, nchunk), dim3(NT), 0, ctx->stream, fixed, df, moving, dm, fixed_mask,
-                       moving_mask, a, ncand, partials, ticket, mail, seq, fsamp);
-  PP_LAUNCH_CHECK(ctx, "k_metric_values");
+    hipLaunchKernelGGL((k_metric_values_lanes<1>), dim3(nb), dim3(NT), 0, ctx->stream, fixed, df, moving, dm, fixed_mask, moving_mask, a,
+                       ncand, (int)spt, partials, ticket, mail, seq, fsamp);
+  PP_LAUNCH_CHECK(ctx, "k_metric_values_lanes");
   memset(result, 0, (size_t)ncand * 6 * sizeof(double));
-  for (int c = 0; c < nchunk; ++c) {
-    const int k = ncand - c * ch < ch ? ncand - c * ch : ch;
+  for (int w = 0; w * cpw < ncand; ++w) {
+    const int k = ncand - w * cpw < cpw ? ncand - w * cpw : cpw;
     double vals[PP_MAIL_ENTRIES];
-    rc = pp_mail_take(ctx, c, k * nv, seq, vals);
+    rc = pp_mail_take(ctx, w, k * nv, seq, vals);
     if (rc) return rc;
     for (int j = 0; j < k; ++j)
-      for (int f = 0; f < nv; ++f) result[((size_t)c * ch + j) * 6 + f] = vals[j * nv + f];
+      for (int f = 0; f < nv; ++f) result[((size_t)w * cpw + j) * 6 + f] = vals[j * nv + f];
   }
   return PP_OK;
 }

@@ -1,20 +1,19 @@
-"""The linear-registration metric kernels (pp_fusion.hip: k_metric_grad, k_metric_affine + k_sum14_final, k_metric_values,
-k_metric_values_lanes, k_mi_histogram, k_mi_gradient, k_fixed_samples) against the fp64 restatement of
+"""The linear-registration metric kernels (pp_fusion.hip: k_metric_grad, k_metric_values_lanes, k_mi_histogram,
+k_mi_gradient + k_sum14_final, k_fixed_samples) against the fp64 restatement of
 tests/linear_metric_restatement.py, on every path of their dispatch ("Linear metric, which lattice enters
 which kernel").  tests/test_linear.py ties them to a reference at one lattice of 158 samples -- one block, one ticket group,
 one fold trip; here every case is the smallest lattice that reaches another path.
 
 The dispatch forest (NT = 256 threads a block, n = samples of the lattice):
-  value + gradient   PP_METRIC_GRAD_ONE_LAUNCH unset / 1: k_metric_grad<MODE, GI>, min(ceil(n / 256), 512) blocks, a thread holds
+  value + gradient   k_metric_grad<MODE, GI>, min(ceil(n / 256), 512) blocks, a thread holds
                      G = 4 samples in flight (2 for correlation and for the packed gradient image), so a second grid-stride
                      trip starts above 512 * 256 * G samples; two-level ticket (block b counts in group b % 8, the last of a group
                      on the top counter); the last block folds floor(256 / NACC) * 16 rows a trip (288 mean squares, 96
-                     correlation); 64-bit lattice arithmetic from 2^31 virtual voxels.  = 0: k_metric_affine + k_sum14_final.
-  value probes       PP_METRIC_LANES unset / 1: k_metric_values_lanes, 16 sample slots a block, spt = samples per thread
+                     correlation); 64-bit lattice arithmetic from 2^31 virtual voxels.
+  value probes       k_metric_values_lanes, 16 sample slots a block, spt = samples per thread
                      (a multiple of 4) so that at most 128 blocks (n < 20000) or 1024 blocks run; folds 128 (mean squares) /
                      32 (correlation) rows a trip; walk<FAST, MASKED>: FAST with the level's fixed-sample cache and 32-bit
-                     offsets (moving nx >= 2), else the plain form.  = 0: k_metric_values<MODE, CH>, CH = 4 candidates a block
-                     row, or the straight-line 16 for mean squares with n >= 150000 and more than 4 candidates.
+                     offsets (moving nx >= 2), else the plain form.
   mutual information k_mi_histogram, k_mi_gradient + k_sum14_final: at most 512 blocks, one sample a thread and trip.
   fixed-sample cache k_fixed_samples, inside pp_linear_optimize_f32 only.
 
@@ -190,30 +189,27 @@ def within(got, want, bound, what):
     assert not bad.any(), (what, np.argwhere(bad)[:5].tolist(), got[bad][:5], want[bad][:5], bound[bad][:5])
 
 
-def grad_calls(be, monkeypatch, a, Am, bm):
-    """Both gradient-bearing entry points under both launch schemes -> {(fn, one_launch): sums}; the second call bit-equal."""
+def grad_calls(be, a, Am, bm):
+    """Both gradient-bearing entry points -> {fn: sums}; the second call bit-equal."""
     out = {}
-    for one in ("0", "1"):
-        monkeypatch.setenv("PP_METRIC_GRAD_ONE_LAUNCH", one)
-        for name in ("meansq_affine", "corr_moments_affine"):
-            fn = getattr(be.ctx, name)
-            r = np.array(fn(a["fixed"], a["fsize"], a["moving"], a["msize"], a["Af"], a["bf"], np.asarray(Am).ravel(), bm, a["vsize"], a["stride"],
-                            fixed_mask=a["fixed_mask"], moving_mask=a["moving_mask"]))
-            again = np.array(fn(a["fixed"], a["fsize"], a["moving"], a["msize"], a["Af"], a["bf"], np.asarray(Am).ravel(), bm, a["vsize"],
-                                a["stride"], fixed_mask=a["fixed_mask"], moving_mask=a["moving_mask"]))
-            assert np.array_equal(r, again), (name, one)
-            out[name, one] = r
-    monkeypatch.delenv("PP_METRIC_GRAD_ONE_LAUNCH", raising=False)
+    for name in ("meansq_affine", "corr_moments_affine"):
+        fn = getattr(be.ctx, name)
+        r = np.array(fn(a["fixed"], a["fsize"], a["moving"], a["msize"], a["Af"], a["bf"], np.asarray(Am).ravel(), bm, a["vsize"], a["stride"],
+                        fixed_mask=a["fixed_mask"], moving_mask=a["moving_mask"]))
+        again = np.array(fn(a["fixed"], a["fsize"], a["moving"], a["msize"], a["Af"], a["bf"], np.asarray(Am).ravel(), bm, a["vsize"],
+                            a["stride"], fixed_mask=a["fixed_mask"], moving_mask=a["moving_mask"]))
+        assert np.array_equal(r, again), name
+        out[name] = r
     return out
 
 
 def check_grad(be, key, path, got, s):
-    for (name, one), r in got.items():
+    for name, r in got.items():
         want, bound = LR.meansq(s) if name == "meansq_affine" else LR.corr(s)
         cnt = 1 if name == "meansq_affine" else 0
-        assert r[cnt] == want[cnt] == s.count, (key, path, name, one, r[cnt], want[cnt])
-        note(be, key, f"{path}:{name}:one_launch={one}", r, want, bound)
-        within(r, want, bound, (key, path, name, one))
+        assert r[cnt] == want[cnt] == s.count, (key, path, name, r[cnt], want[cnt])
+        note(be, key, f"{path}:{name}", r, want, bound)
+        within(r, want, bound, (key, path, name))
 
 
 # --------------------------------------------------------------------------------------
@@ -304,85 +300,81 @@ def test_restatement_agrees_with_the_oracle(key):
 
 
 @pytest.mark.parametrize("key", ALL)
-def test_gradient_kernels(backend, monkeypatch, key):
-    """pp_meansq_affine_f32 / pp_corr_moments_affine_f32, one launch and two, both masks: counts equal, every sum within its
-    bound, the second call bit-equal."""
+def test_gradient_kernels(backend, key):
+    """pp_meansq_affine_f32 / pp_corr_moments_affine_f32, both masks: counts equal, every sum within its bound, the second
+    call bit-equal."""
     s = reference(key)
     assert s.count > (4 if key == "flat" else 50) and s.count < 0.8 * SAMPLES[key]
     a = call_args(backend, key)
-    check_grad(backend, key, "grad", grad_calls(backend, monkeypatch, a, CASES[key]["Am"], CASES[key]["bm"]), s)
+    check_grad(backend, key, "grad", grad_calls(backend, a, CASES[key]["Am"], CASES[key]["bm"]), s)
 
 
 @pytest.mark.parametrize("key", SOME)
 @pytest.mark.parametrize("masks", ["", "f", "m"])
-def test_mask_combinations(backend, monkeypatch, key, masks):
+def test_mask_combinations(backend, key, masks):
     s, both = reference(key, masks=masks), reference(key)
     assert s.count > both.count
     a = call_args(backend, key, masks)
-    check_grad(backend, key, "masks=" + (masks or "none"), grad_calls(backend, monkeypatch, a, CASES[key]["Am"], CASES[key]["bm"]), s)
+    check_grad(backend, key, "masks=" + (masks or "none"), grad_calls(backend, a, CASES[key]["Am"], CASES[key]["bm"]), s)
     for metric in (0, 1):
-        for lanes in ("0", "1"):
-            monkeypatch.setenv("PP_METRIC_LANES", lanes)
-            Am, bm = candidates(key)[1]
-            r = backend.ctx.metric_values_affine(metric, a["fixed"], a["fsize"], a["moving"], a["msize"], a["Af"], a["bf"], [CASES[key]["Am"], Am],
-                                                 [CASES[key]["bm"], bm], a["vsize"], a["stride"], fixed_mask=a["fixed_mask"], moving_mask=a["moving_mask"])
-            for row, sc in ((0, s), (1, reference(key, masks=masks, cand=1))):
-                want, bound = LR.values(metric, sc)
-                assert r[row, 1 - metric] == sc.count
-                within(r[row], want, bound, (key, masks, metric, lanes, row))
+        Am, bm = candidates(key)[1]
+        r = backend.ctx.metric_values_affine(metric, a["fixed"], a["fsize"], a["moving"], a["msize"], a["Af"], a["bf"], [CASES[key]["Am"], Am],
+                                             [CASES[key]["bm"], bm], a["vsize"], a["stride"], fixed_mask=a["fixed_mask"], moving_mask=a["moving_mask"])
+        for row, sc in ((0, s), (1, reference(key, masks=masks, cand=1))):
+            want, bound = LR.values(metric, sc)
+            assert r[row, 1 - metric] == sc.count
+            within(r[row], want, bound, (key, masks, metric, row))
 
 
 @pytest.mark.parametrize("key", SOME)
 def test_gradient_image(backend, monkeypatch, key):
-    """The filtered-gradient-image paths (k_metric_grad<., 1> planar, <., 2> packed, k_metric_affine's branch), both masks."""
+    """The filtered-gradient-image paths (k_metric_grad<., 1> planar, <., 2> packed), both masks."""
     c = CASES[key]
     F, M, fm, mm, GI, _ = data(key)
     s = reference(key, gimg=True)
     a = call_args(backend, key)
-    plain = grad_calls(backend, monkeypatch, a, c["Am"], c["bm"])
+    plain = grad_calls(backend, a, c["Am"], c["bm"])
     dgi = backend.dev(GI)
     packed = backend.dev(np.ascontiguousarray(np.concatenate([np.moveaxis(GI, 0, -1), M[..., None]], axis=-1)))
     try:
         backend.ctx.set_moving_gradient(dgi, a["msize"], packed=packed)
         monkeypatch.setenv("PP_METRIC_GRAD_PLANAR", "1")
-        planar = grad_calls(backend, monkeypatch, a, c["Am"], c["bm"])
+        planar = grad_calls(backend, a, c["Am"], c["bm"])
         monkeypatch.delenv("PP_METRIC_GRAD_PLANAR", raising=False)
-        pack = grad_calls(backend, monkeypatch, a, c["Am"], c["bm"])
+        pack = grad_calls(backend, a, c["Am"], c["bm"])
     finally:
         backend.ctx.set_moving_gradient(None)
     check_grad(backend, key, "gimg:planar", planar, s)
     check_grad(backend, key, "gimg:packed", pack, s)
     for k in planar:
         np.testing.assert_allclose(pack[k], planar[k], rtol=0, atol=1e-12 * np.abs(planar[k]).max())
-        nval = 2 if k[0] == "meansq_affine" else 6
+        nval = 2 if k == "meansq_affine" else 6
         np.testing.assert_allclose(planar[k][:nval], plain[k][:nval], rtol=0, atol=1e-12 * np.abs(plain[k][:nval]).max())
         assert np.abs(planar[k][nval:] - plain[k][nval:]).max() > 1e-2 * np.abs(plain[k][nval:]).max()
-    after = grad_calls(backend, monkeypatch, a, c["Am"], c["bm"])
+    after = grad_calls(backend, a, c["Am"], c["bm"])
     for k in plain:
         assert np.array_equal(after[k], plain[k])
 
 
 @pytest.mark.parametrize("key", SOME)
-def test_sample_jitter(backend, monkeypatch, key):
+def test_sample_jitter(backend, key):
     """Every entry point at lattice index + jitter (a seeded N(0, 1/3) array, taken as given); without the array, the plain bits."""
     c = CASES[key]
     jit = data(key)[5]
     s = reference(key, jitter=True)
     a = call_args(backend, key)
-    plain = grad_calls(backend, monkeypatch, a, c["Am"], c["bm"])
+    plain = grad_calls(backend, a, c["Am"], c["bm"])
     dj = backend.dev(jit)
     try:
         backend.ctx.set_sample_jitter(dj)
-        got = grad_calls(backend, monkeypatch, a, c["Am"], c["bm"])
+        got = grad_calls(backend, a, c["Am"], c["bm"])
         check_grad(backend, key, "jitter", got, s)
         for metric in (0, 1):
-            for lanes in ("0", "1"):
-                monkeypatch.setenv("PP_METRIC_LANES", lanes)
-                r = backend.ctx.metric_values_affine(metric, a["fixed"], a["fsize"], a["moving"], a["msize"], a["Af"], a["bf"], [c["Am"]], [c["bm"]],
-                                                     a["vsize"], a["stride"], fixed_mask=a["fixed_mask"], moving_mask=a["moving_mask"])
-                want, bound = LR.values(metric, s)
-                assert r[0, 1 - metric] == s.count
-                within(r[0], want, bound, (key, "jitter", metric, lanes))
+            r = backend.ctx.metric_values_affine(metric, a["fixed"], a["fsize"], a["moving"], a["msize"], a["Af"], a["bf"], [c["Am"]], [c["bm"]],
+                                                 a["vsize"], a["stride"], fixed_mask=a["fixed_mask"], moving_mask=a["moving_mask"])
+            want, bound = LR.values(metric, s)
+            assert r[0, 1 - metric] == s.count
+            within(r[0], want, bound, (key, "jitter", metric))
         for kernel, nbins in ((0, 50), (1, 20)):
             b, bd = mi_bins(key, kernel, nbins)
             hist, count = backend.ctx.mi_histogram(a["fixed"], a["fsize"], a["moving"], a["msize"], a["Af"], a["bf"], c["Am"].ravel(), c["bm"],
@@ -392,8 +384,8 @@ def test_sample_jitter(backend, monkeypatch, key):
             within(hist, want, bound, (key, "jitter", "mi", kernel))
     finally:
         backend.ctx.set_sample_jitter(None)
-    assert got["meansq_affine", "1"][1] != plain["meansq_affine", "1"][1] or got["meansq_affine", "1"][0] != plain["meansq_affine", "1"][0]
-    after = grad_calls(backend, monkeypatch, a, c["Am"], c["bm"])
+    assert got["meansq_affine"][1] != plain["meansq_affine"][1] or got["meansq_affine"][0] != plain["meansq_affine"][0]
+    after = grad_calls(backend, a, c["Am"], c["bm"])
     for k in plain:
         assert np.array_equal(after[k], plain[k])
 
@@ -412,14 +404,14 @@ def _probe_params():
 
 
 @pytest.mark.parametrize("backend,key", _probe_params(), indirect=["backend"])
-def test_value_probes(backend, monkeypatch, key):
-    """pp_metric_values_affine_f32, both metrics, lane kernel and candidate-loop kernels, 1 .. 16 candidates (the chunk sizes 4
-    and 16, two to four mailbox writers): counts equal, values within bound, candidate 0 = the gradient-bearing call,
-    candidate 2 (no overlap) exactly zero, and a candidate's bits independent of its companions."""
+def test_value_probes(backend, key):
+    """pp_metric_values_affine_f32, both metrics, 1 .. 16 candidates (one or two mailbox writers): counts equal, values
+    within bound, candidate 0 = the gradient-bearing call, candidate 2 (no overlap) exactly zero, and a candidate's bits
+    independent of its companions."""
     c = CASES[key]
     cand = candidates(key)
     a = call_args(backend, key)
-    grad = grad_calls(backend, monkeypatch, a, c["Am"], c["bm"])
+    grad = grad_calls(backend, a, c["Am"], c["bm"])
     ncs = (3, 16) if key == "strided" else NCAND
     refs = {k: reference(key, cand=k) for k in range(16) if k != 2}
     assert len({refs[k].count for k in refs}) > (2 if key == "flat" else 8)                 # the perturbations move samples across borders and mask voxels
@@ -431,37 +423,33 @@ def test_value_probes(backend, monkeypatch, key):
 
     for metric in (0, 1):
         cnt, nv = 1 - metric, 2 if metric == 0 else 6
-        first = grad["meansq_affine", "1"][:2] if metric == 0 else grad["corr_moments_affine", "1"][:6]
-        for lanes in ("0", "1"):
-            monkeypatch.setenv("PP_METRIC_LANES", lanes)
-            rows = {}
-            for n in ncs:
-                r = run(metric, cand[:n])
-                assert r.shape == (n, 6) and np.isfinite(r).all()
-                for k in range(n):
-                    if k == 2:
-                        assert np.array_equal(r[k], np.zeros(6)), (key, metric, lanes, n, r[k])
-                        continue
-                    want, bound = LR.values(metric, refs[k])
-                    assert r[k, cnt] == refs[k].count, (key, metric, lanes, n, k, r[k, cnt], refs[k].count)
-                    within(r[k], want, bound, (key, metric, lanes, n, k))
-                    assert np.array_equal(r[k, nv:], np.zeros(6 - nv))
-                    if k in rows:     # the same candidate in a smaller batch: the same sums in (at most) another order ...
-                        np.testing.assert_allclose(r[k], rows[k], rtol=0, atol=1e-12 * np.abs(rows[k]).max())
-                        if lanes == "1":                  # ... and the lane kernel's layout does not depend on the batch
-                            assert np.array_equal(r[k], rows[k]), (key, metric, n, k)
-                    rows[k] = r[k]
-                np.testing.assert_allclose(r[0, :nv], first, rtol=0, atol=1e-12 * np.abs(first).max())
-                assert r[0, cnt] == first[cnt]
-                assert np.array_equal(run(metric, cand[:n]), r)
-                if n in (3, 5, 16):     # other companions in the other slots: the same bits
-                    other = list(cand[:n])
-                    keep = 1 if n == 3 else 4
-                    swapped = [other[keep] if i == keep else cand[(i + 7) % 16] for i in range(n)]
-                    assert np.array_equal(run(metric, swapped)[keep], r[keep]), (key, metric, lanes, n)
-            big = ncs[-1]
-            want, bound = LR.values(metric, refs[0])
-            note(backend, key, f"values:metric={metric}:lanes={lanes}", run(metric, cand[:big])[0], want, bound)
+        first = grad["meansq_affine"][:2] if metric == 0 else grad["corr_moments_affine"][:6]
+        rows = {}
+        for n in ncs:
+            r = run(metric, cand[:n])
+            assert r.shape == (n, 6) and np.isfinite(r).all()
+            for k in range(n):
+                if k == 2:
+                    assert np.array_equal(r[k], np.zeros(6)), (key, metric, n, r[k])
+                    continue
+                want, bound = LR.values(metric, refs[k])
+                assert r[k, cnt] == refs[k].count, (key, metric, n, k, r[k, cnt], refs[k].count)
+                within(r[k], want, bound, (key, metric, n, k))
+                assert np.array_equal(r[k, nv:], np.zeros(6 - nv))
+                if k in rows:     # the same candidate in a smaller batch: the lane kernel's layout does not depend on the batch
+                    assert np.array_equal(r[k], rows[k]), (key, metric, n, k)
+                rows[k] = r[k]
+            np.testing.assert_allclose(r[0, :nv], first, rtol=0, atol=1e-12 * np.abs(first).max())
+            assert r[0, cnt] == first[cnt]
+            assert np.array_equal(run(metric, cand[:n]), r)
+            if n in (3, 5, 16):     # other companions in the other slots: the same bits
+                other = list(cand[:n])
+                keep = 1 if n == 3 else 4
+                swapped = [other[keep] if i == keep else cand[(i + 7) % 16] for i in range(n)]
+                assert np.array_equal(run(metric, swapped)[keep], r[keep]), (key, metric, n)
+        big = ncs[-1]
+        want, bound = LR.values(metric, refs[0])
+        note(backend, key, f"values:metric={metric}", run(metric, cand[:big])[0], want, bound)
 
 
 # --------------------------------------------------------------------------------------
@@ -564,25 +552,22 @@ def test_inf_nan_under_rejected_samples(backend, monkeypatch, key):
 
     def run(F_, M_, GI_):
         a = dict(call_args(backend, key), fixed=backend.dev(F_), moving=backend.dev(M_), fixed_mask=backend.dev(fm), moving_mask=backend.dev(mm))
-        out = [grad_calls(backend, monkeypatch, a, c["Am"], c["bm"])]
+        out = [grad_calls(backend, a, c["Am"], c["bm"])]
         dgi = backend.dev(GI_)
         packed = backend.dev(np.ascontiguousarray(np.concatenate([np.moveaxis(GI_, 0, -1), M_[..., None]], axis=-1)))
         try:
             backend.ctx.set_moving_gradient(dgi, a["msize"], packed=packed)
-            out.append(grad_calls(backend, monkeypatch, a, c["Am"], c["bm"]))
+            out.append(grad_calls(backend, a, c["Am"], c["bm"]))
             monkeypatch.setenv("PP_METRIC_GRAD_PLANAR", "1")
-            out.append(grad_calls(backend, monkeypatch, a, c["Am"], c["bm"]))
+            out.append(grad_calls(backend, a, c["Am"], c["bm"]))
         finally:
             monkeypatch.delenv("PP_METRIC_GRAD_PLANAR", raising=False)
             backend.ctx.set_moving_gradient(None)
         probes = {}
         for metric in (0, 1):
-            for lanes in ("0", "1"):
-                monkeypatch.setenv("PP_METRIC_LANES", lanes)
-                probes[metric, lanes] = backend.ctx.metric_values_affine(metric, a["fixed"], a["fsize"], a["moving"], a["msize"], a["Af"], a["bf"],
-                                                                         [m[0] for m in cand], [m[1] for m in cand], a["vsize"], a["stride"],
-                                                                         fixed_mask=a["fixed_mask"], moving_mask=a["moving_mask"])
-        monkeypatch.delenv("PP_METRIC_LANES", raising=False)
+            probes[metric] = backend.ctx.metric_values_affine(metric, a["fixed"], a["fsize"], a["moving"], a["msize"], a["Af"], a["bf"],
+                                                              [m[0] for m in cand], [m[1] for m in cand], a["vsize"], a["stride"],
+                                                              fixed_mask=a["fixed_mask"], moving_mask=a["moving_mask"])
         return out, probes
 
     (clean, clean_p), (dirty, dirty_p) = run(F, M, GI), run(Fp, Mp, GIp)

@@ -269,22 +269,11 @@ def test_cc_row_lengths(backend, nx):
 
 
 @pytest.mark.parametrize("nx", ROW_NX + [2049, 4100])
-def test_cc_rows_block_form(backend, nx, monkeypatch):
-    """PP_CC_ROWS_BLOCK=1, the block-per-row form of stage 1 (2048-voxel passes): equal to the default form and scipy."""
-    masks = [_row_case(nx, 2048), 1 - _row_case(nx, 512)]
-    default = [check_cc(backend, m, f"default nx {nx}") for m in masks]
-    monkeypatch.setenv("PP_CC_ROWS_BLOCK", "1")
-    for m, d in zip(masks, default):
-        got = check_cc(backend, m, f"block form nx {nx}")
-        for fill in (True, False):
-            np.testing.assert_array_equal(got[fill][0], d[fill][0])
-            assert got[fill][1] == d[fill][1]
-
-
-def test_cc_rows_block_form_on_volumes(backend, monkeypatch):
-    monkeypatch.setenv("PP_CC_ROWS_BLOCK", "1")
-    check_cc(backend, random_runs((9, 14, 70), 3), "block form, runs")
-    check_cc(backend, serpentine((7, 9, 40)), "block form, serpentine")
+def test_cc_rows_with_run_boundaries_at_2048(backend, nx):
+    """The same row lengths and two rows of several passes (2049, 4100) with the run boundaries placed around multiples of
+    2048 voxels, and the complement of the 512-voxel cases."""
+    for m in (_row_case(nx, 2048), 1 - _row_case(nx, 512)):
+        check_cc(backend, m, f"nx {nx}")
 
 
 def test_cc_degenerate_volumes(backend):
