@@ -1156,12 +1156,13 @@ int pp_weight_map_block_f32(pp_ctx* ctx, const float* target, const float* movin
   PP_REQUIRE(ctx, target && moving && weight && size && radius, "pp_weight_map_block_f32: NULL argument");
   const size_t N = pp_nvox(size);
   PP_REQUIRE(ctx, N > 0, "pp_weight_map_block_f32: empty volume");
+  for (int a = 0; a < 3; ++a)   // (before the first launch: a refused call writes nothing)
+    PP_REQUIRE(ctx, radius[a] >= 0 && radius[a] <= PP_MAX_RADIUS, "pp_weight_map_block_f32: box radius out of range");
   launch_map4(ctx, N, all_aligned16(target, moving, weight), op_sqdiff{target, moving, weight});
   PP_LAUNCH_CHECK(ctx, "k_map4<op_sqdiff>");
   // sitk.BoxMean(square, radius): the mean over a (2r+1)^3 box with ZeroFluxNeumann edges is three 1-D means
   pp_taps taps[3];
   for (int a = 0; a < 3; ++a) {
-    PP_REQUIRE(ctx, radius[a] >= 0 && radius[a] <= PP_MAX_RADIUS, "pp_weight_map_block_f32: box radius out of range");
     taps[a].r = radius[a];
     for (int k = 0; k < 2 * radius[a] + 1; ++k) taps[a].w[k] = 1.0f / (float)(2 * radius[a] + 1);
   }
