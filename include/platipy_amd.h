@@ -629,6 +629,31 @@ int pp_slice_moments_u8(pp_ctx* ctx, const uint8_t* const* masks, int nmasks, co
 int pp_tube_mask_u8(pp_ctx* ctx, const double* points, int npoints, const int size[3], const double spacing[3],
                     const double origin[3], double radius, uint8_t* out);
 
+/* ---- RTSTRUCT contours -------------------------------------------------------------- */
+/* Closed planar contours to binary masks: what the loop of skimage.draw.polygon calls and XORs does at
+ * dicom/io/rtstruct_to_nifti.py:105-217, for all structures and all slices in ONE call.  vertices: HOST, nverts x 2 int32
+ * (x, y) pixel indices, already rounded (the reference rounds them too, :172-180), each within +-2^24.  contours: HOST,
+ * ncontours entries {first, count, structure, z}: the vertices first ... first + count - 1 (count >= 1) are one closed
+ * polygon on slice z (0 ... size[2] - 1) of structure `structure` (0 ... nstructures - 1).  out: DEVICE, uint8
+ * [nstructures][size[2]][size[1]][size[0]]; the call defines EVERY byte of it (1 inside, 0 elsewhere), the caller does not
+ * clear it.  A pixel is inside a contour by scikit-image's point_in_polygon (the closed polygon for simple polygons: interior,
+ * edges and vertices; recalled from upstream, UNVERIFIED here, parity with scikit-image UNPINNED), evaluated in exact
+ * integers: no division, no floating point.  Contours of one structure on one slice combine by XOR (:209), so an inner contour
+ * cuts a hole and the same contour twice gives nothing.  Pixels are clipped to the true slice [0, size[0]) x [0, size[1]) -- a
+ * deviation: the reference passes shape = (ny, nx) to a call whose rows are x.  No contours at all is valid (all zeros).
+ * One workgroup per 64 x 64 tile of a (structure, slice)'s bounding box, edges staged into LDS PP_CONTOUR_CHUNK at a time,
+ * any count works; the rest of `out` is one memset on the same stream.  Nothing is atomic: reruns are bit-identical.
+ * PP_ERR_ARG for a NULL table, a negative count, nstructures < 1, an empty volume, a contour outside the vertex table, a
+ * structure or slice out of range, a vertex beyond +-2^24 (`out` is then untouched); an axis longer than 2^24: PP_ERR_SIZE.
+ * Synchronises (the tables are host memory of the call). */
+#define PP_CONTOUR_CHUNK 256
+typedef struct {
+  int32_t first, count; /* vertices of the contour */
+  int32_t structure, z; /* the mask and the slice it is XORed into */
+} pp_contour;
+int pp_contour_fill_u8(pp_ctx* ctx, const int32_t* vertices, int nverts, const pp_contour* contours, int ncontours,
+                       const int size[3], int nstructures, uint8_t* out);
+
 /* ---- region primitives (airway and lung segmentation) ------------------------------- */
 /* sitk.ConnectedComponent(mask) with face connectivity (imaging/utils/lung.py:41-42, projects/bronchus/bronchus.py:214 and
  * :331-333): labels (DEVICE, int32, `size` voxels) = 0 on background (mask == 0), and 1 ... N on the components, numbered in

@@ -116,6 +116,10 @@ SURFACE_STATS_DTYPE = np.dtype([("count", "<i8"), ("count_le_tau", "<i8"), ("sum
                                 ("max", "<f4"), ("range_lo", "<f4"), ("range_hi", "<f4"), ("hist", "<i8", (SURFACE_BINS,))])
 
 
+# pp_contour, and the two constants of pp_contour_fill_u8: edges staged per pass (PP_CONTOUR_CHUNK), the vertex bound
+CONTOUR_DTYPE = np.dtype([("first", "<i4"), ("count", "<i4"), ("structure", "<i4"), ("z", "<i4")])
+CONTOUR_CHUNK, CONTOUR_MAX_INDEX = 256, 1 << 24
+
 DOSE_MAX_LABELS, DOSE_MAX_BINS, ORDER_STATS_MAX_RANKS = 64, 1 << 20, 8
 # pp_dose_stats as a numpy record
 DOSE_STATS_DTYPE = np.dtype([("count", "<i8"), ("mask_sum", "<i8"), ("dose_sum", "<f8"), ("dose_min", "<f4"), ("dose_max", "<f4")])
@@ -241,6 +245,7 @@ _SIGNATURES = {
     "pp_slice_moments_u8": (C.c_int, [_P, C.POINTER(_P), C.c_int, C.POINTER(C.c_int), C.c_int, _P]),
     "pp_tube_mask_u8": (C.c_int, [_P, C.POINTER(C.c_double), C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_double), C.POINTER(C.c_double),
                                   C.c_double, _P]),
+    "pp_contour_fill_u8": (C.c_int, [_P, _P, C.c_int, _P, C.c_int, C.POINTER(C.c_int), C.c_int, _P]),
     "pp_connected_components_u8": (C.c_int, [_P, _P, C.POINTER(C.c_int), _P, C.POINTER(C.c_int)]),
     "pp_connected_components_conn_u8": (C.c_int, [_P, _P, C.POINTER(C.c_int), C.c_int, _P, C.POINTER(C.c_int)]),
     "pp_slice_convex_hull_u8": (C.c_int, [_P, _P, C.POINTER(C.c_int), _P]),
@@ -747,6 +752,30 @@ class Context:
         p = np.ascontiguousarray(points, dtype=np.float64).reshape(-1, 3)
         self._chk_value(self.lib.pp_tube_mask_u8(self.h, p.ctypes.data_as(C.POINTER(C.c_double)), int(p.shape[0]), _i3(size), _d3(spacing),
                                                  _d3(origin), float(radius), ptr(out)), "pp_tube_mask_u8")
+
+    # -- RTSTRUCT contours -------------------------------------------------------------
+    def contour_fill(self, vertices, contours, size, nstructures, out):
+        """pp_contour_fill_u8: out (uint8 [nstructures][Z][Y][X], every byte written) = the XOR of the closed polygons of each
+        (structure, slice).  vertices: [n, 2] int32 (x, y) pixel indices on the host; contours: (first, count, structure, z)
+        rows (or a CONTOUR_DTYPE array).  ValueError for a vertex beyond +-2^24, a contour outside the vertex table, a
+        structure or slice out of range, a buffer that does not hold nstructures volumes.  Synchronises."""
+        if isinstance(vertices, np.ndarray) and vertices.dtype == np.int32:
+            v = np.ascontiguousarray(vertices).reshape(-1, 2)
+        else:
+            v = np.ascontiguousarray(vertices, dtype=np.int64).reshape(-1, 2)
+            if v.size and int(np.abs(v).max()) > 0x7fffffff:     # (the cast to int32 would wrap it; the library refuses the rest)
+                raise ValueError(f"contour_fill: a vertex index beyond +-2^24 ({int(np.abs(v).max())})")
+            v = v.astype(np.int32)
+        ct = contours if isinstance(contours, np.ndarray) and contours.dtype == CONTOUR_DTYPE else \
+            np.array([tuple(int(x) for x in c) for c in contours], dtype=CONTOUR_DTYPE)
+        ct = np.ascontiguousarray(ct).reshape(-1)
+        _check_volume("contour_fill", size)
+        have = _nbytes(out)
+        if have is not None and have != int(nstructures) * int(size[0]) * int(size[1]) * int(size[2]):
+            raise ValueError(f"contour_fill: `out` does not hold {nstructures} volumes of {tuple(size)} ({have} bytes)")
+        self._chk_value(self.lib.pp_contour_fill_u8(self.h, v.ctypes.data if v.size else None, int(v.shape[0]),
+                                                    ct.ctypes.data if ct.size else None, int(ct.size), _i3(size), int(nstructures), ptr(out)),
+                        "pp_contour_fill_u8")
 
     # -- region primitives ------------------------------------------------------------
     def connected_components(self, mask, size, labels, want_count=True):

@@ -1577,3 +1577,6 @@ int pp_linear_set_sample_jitter(pp_ctx* ctx, const float* jitter, size_t nsample
 
 // vessel splining (imaging/utils/vessel.py): pp_slice_moments_u8, pp_tube_mask_u8
 #include "pp_vessel.h"
+
+// RTSTRUCT contours to masks (dicom/io/rtstruct_to_nifti.py): pp_contour_fill_u8
+#include "pp_contour.h"
