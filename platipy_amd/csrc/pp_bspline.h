@@ -42,6 +42,8 @@
 // 512 x 256, 30 bins, mesh 8 x 8 x 4 / 32 x 32 x 16, rate 1.0): pass 1 5.0 / 6.0 ms, pass 2 47.5 / 34.3 ms beside 46.1 / 33.1 ms for mean squares.
 #pragma once
 
+#include "pp_reduce.h"
+
 namespace {
 
 constexpr int BSP_NT = 256;
@@ -521,12 +523,9 @@ __global__ void __launch_bounds__(BSP_NT) k_bsp_scalars(const double* __restrict
   for (int i = threadIdx.x; i < nrows; i += BSP_NT)
     for (int q = 0; q < BSP_NSCAL; ++q) acc[q] += partial[(size_t)i * row + off + q];
   for (int q = 0; q < BSP_NSCAL; ++q) red[q * BSP_NT + threadIdx.x] = acc[q];
-  __syncthreads();
-  for (int s = BSP_NT / 2; s > 0; s >>= 1) {
-    if ((int)threadIdx.x < s)
-      for (int q = 0; q < BSP_NSCAL; ++q) red[q * BSP_NT + threadIdx.x] += red[q * BSP_NT + threadIdx.x + s];
-    __syncthreads();
-  }
+  pp_block_tree<BSP_NT>((int)threadIdx.x, [&](int a, int b) {
+    for (int q = 0; q < BSP_NSCAL; ++q) red[q * BSP_NT + a] += red[q * BSP_NT + b];
+  });
   if ((int)threadIdx.x < BSP_NSCAL) out[threadIdx.x] = red[threadIdx.x * BSP_NT];
 }
 

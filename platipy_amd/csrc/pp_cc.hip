@@ -14,6 +14,7 @@
 // it voxel by voxel serialises on its root (12 ms at 512x512x256; 10x less in stages).
 #include "pp_internal.h"
 #include "pp_kernels.h"
+#include "pp_reduce.h"
 
 namespace {
 
@@ -186,65 +187,40 @@ __global__ void __launch_bounds__(NT) k_cc_count(const uint8_t* __restrict__ mas
   }
 }
 
-// arg max over roots of (count, -root): partials [grid][2] then a single-block fold.
-__global__ void __launch_bounds__(NT) k_cc_argmax(const uint8_t* __restrict__ mask, const int* __restrict__ L,
-                                                  const int* __restrict__ count, size_t n, int* __restrict__ partials) {
-  __shared__ int bc[NT], br[NT];
-  int c = 0, r = 0x7fffffff;
-  for (size_t i = (size_t)blockIdx.x * NT + threadIdx.x; i < n; i += (size_t)gridDim.x * NT)
-    if (mask[i] && L[i] == (int)i) {
-      const int ci = count[i];
-      if (ci > c || (ci == c && (int)i < r)) {
-        c = ci;
-        r = (int)i;
-      }
-    }
-  bc[threadIdx.x] = c;
-  br[threadIdx.x] = r;
-  __syncthreads();
-  for (int s = NT / 2; s > 0; s >>= 1) {
-    if ((int)threadIdx.x < s) {
-      const int c2 = bc[threadIdx.x + s], r2 = br[threadIdx.x + s];
-      if (c2 > bc[threadIdx.x] || (c2 == bc[threadIdx.x] && r2 < br[threadIdx.x])) {
-        bc[threadIdx.x] = c2;
-        br[threadIdx.x] = r2;
-      }
-    }
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) {
-    partials[2 * blockIdx.x] = bc[0];
-    partials[2 * blockIdx.x + 1] = br[0];
+// arg max over roots of (count, -root): partials [grid][2] then a single-block fold.  The rule, written once: candidate
+// (c2, r2) replaces (c, r) when its count is larger, or equal with the smaller root.
+__device__ __forceinline__ void cc_argmax_take(int& c, int& r, int c2, int r2) {
+  if (c2 > c || (c2 == c && r2 < r)) {
+    c = c2;
+    r = r2;
   }
 }
 
-__global__ void __launch_bounds__(NT) k_cc_argmax_final(const int* __restrict__ partials, int nb, int* __restrict__ result) {
+// the threads' candidates folded by the block tree; thread 0 stores the winner's {count, root} at pair[0..1]
+__device__ __forceinline__ void cc_block_argmax_store(int c, int r, int* __restrict__ pair) {
   __shared__ int bc[NT], br[NT];
+  const int t = threadIdx.x;
+  bc[t] = c;
+  br[t] = r;
+  pp_block_tree<NT>(t, [&](int a, int b) { cc_argmax_take(bc[a], br[a], bc[b], br[b]); });
+  if (t == 0) {
+    pair[0] = bc[0];
+    pair[1] = br[0];
+  }
+}
+
+__global__ void __launch_bounds__(NT) k_cc_argmax(const uint8_t* __restrict__ mask, const int* __restrict__ L,
+                                                  const int* __restrict__ count, size_t n, int* __restrict__ partials) {
   int c = 0, r = 0x7fffffff;
-  for (int i = threadIdx.x; i < nb; i += NT) {
-    const int ci = partials[2 * i], ri = partials[2 * i + 1];
-    if (ci > c || (ci == c && ri < r)) {
-      c = ci;
-      r = ri;
-    }
-  }
-  bc[threadIdx.x] = c;
-  br[threadIdx.x] = r;
-  __syncthreads();
-  for (int s = NT / 2; s > 0; s >>= 1) {
-    if ((int)threadIdx.x < s) {
-      const int c2 = bc[threadIdx.x + s], r2 = br[threadIdx.x + s];
-      if (c2 > bc[threadIdx.x] || (c2 == bc[threadIdx.x] && r2 < br[threadIdx.x])) {
-        bc[threadIdx.x] = c2;
-        br[threadIdx.x] = r2;
-      }
-    }
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) {
-    result[0] = bc[0];
-    result[1] = br[0];
-  }
+  for (size_t i = (size_t)blockIdx.x * NT + threadIdx.x; i < n; i += (size_t)gridDim.x * NT)
+    if (mask[i] && L[i] == (int)i) cc_argmax_take(c, r, count[i], (int)i);
+  cc_block_argmax_store(c, r, partials + 2 * (size_t)blockIdx.x);
+}
+
+__global__ void __launch_bounds__(NT) k_cc_argmax_final(const int* __restrict__ partials, int nb, int* __restrict__ result) {
+  int c = 0, r = 0x7fffffff;
+  for (int i = threadIdx.x; i < nb; i += NT) cc_argmax_take(c, r, partials[2 * i], partials[2 * i + 1]);
+  cc_block_argmax_store(c, r, result);
 }
 
 __global__ void __launch_bounds__(NT) k_cc_select(const uint8_t* __restrict__ mask, const int* __restrict__ L,

@@ -15,6 +15,8 @@
 // rerun gives the same bits.
 #pragma once
 
+#include "pp_reduce.h"
+
 namespace {
 
 constexpr int CMP_BINS = PP_SURFACE_BINS;
@@ -53,12 +55,9 @@ __global__ void __launch_bounds__(NT) k_overlap_counts(const uint8_t* __restrict
   red[0][t] = ca;
   red[1][t] = cb;
   red[2][t] = cab;
-  __syncthreads();
-  for (int s = NT / 2; s > 0; s >>= 1) {
-    if (t < s)
-      for (int f = 0; f < 3; ++f) red[f][t] += red[f][t + s];
-    __syncthreads();
-  }
+  pp_block_tree<NT>(t, [&](int a, int b) {
+    for (int f = 0; f < 3; ++f) red[f][a] += red[f][b];
+  });
   if (t < 3 && red[t][0]) atomicAdd(&counts[t], red[t][0]);
 }
 
@@ -79,52 +78,13 @@ __global__ void __launch_bounds__(NT) k_contour4(const uint8_t* __restrict__ mas
 
 // min / max of |in|: partials[2 b] = min, [2 b + 1] = max of block b
 __global__ void __launch_bounds__(NT) k_abs_range_partial(const float* __restrict__ in, size_t n, float* __restrict__ partials) {
-  __shared__ float smin[NT], smax[NT];
   float lo = FLT_MAX, hi = -FLT_MAX;
   for (size_t i = (size_t)blockIdx.x * NT + threadIdx.x; i < n; i += (size_t)gridDim.x * NT) {
     const float v = fabsf(in[i]);
     lo = fminf(lo, v);
     hi = fmaxf(hi, v);
   }
-  const int t = threadIdx.x;
-  smin[t] = lo;
-  smax[t] = hi;
-  __syncthreads();
-  for (int s = NT / 2; s > 0; s >>= 1) {
-    if (t < s) {
-      smin[t] = fminf(smin[t], smin[t + s]);
-      smax[t] = fmaxf(smax[t], smax[t + s]);
-    }
-    __syncthreads();
-  }
-  if (t == 0) {
-    partials[2 * (size_t)blockIdx.x] = smin[0];
-    partials[2 * (size_t)blockIdx.x + 1] = smax[0];
-  }
-}
-
-__global__ void __launch_bounds__(NT) k_abs_range_final(const float* __restrict__ partials, int nb, float* __restrict__ range) {
-  __shared__ float smin[NT], smax[NT];
-  float lo = FLT_MAX, hi = -FLT_MAX;
-  for (int b = threadIdx.x; b < nb; b += NT) {
-    lo = fminf(lo, partials[2 * b]);
-    hi = fmaxf(hi, partials[2 * b + 1]);
-  }
-  const int t = threadIdx.x;
-  smin[t] = lo;
-  smax[t] = hi;
-  __syncthreads();
-  for (int s = NT / 2; s > 0; s >>= 1) {
-    if (t < s) {
-      smin[t] = fminf(smin[t], smin[t + s]);
-      smax[t] = fmaxf(smax[t], smax[t + s]);
-    }
-    __syncthreads();
-  }
-  if (t == 0) {
-    range[0] = smin[0];
-    range[1] = smax[0];
-  }
+  pp_block_range_store<NT>(lo, hi, partials + 2 * (size_t)blockIdx.x);
 }
 
 // what one thread, one block (partials[b]) or the whole pass knows about its samples
@@ -141,16 +101,6 @@ __device__ __forceinline__ void surf_merge(surf_acc& a, const surf_acc& b) {
   a.sumsq += b.sumsq;
   a.lo = fminf(a.lo, b.lo);
   a.hi = fmaxf(a.hi, b.hi);
-}
-
-// block tree over sm[NT]; the result is sm[0]
-__device__ __forceinline__ void surf_block_tree(surf_acc* sm) {
-  const int t = threadIdx.x;
-  __syncthreads();
-  for (int s = NT / 2; s > 0; s >>= 1) {
-    if (t < s) surf_merge(sm[t], sm[t + s]);
-    __syncthreads();
-  }
 }
 
 // the histogram's range and the tau test, in fp64 like ITK's histogram and the reference's `dist <= tau`
@@ -219,7 +169,7 @@ __global__ void __launch_bounds__(NT) k_surface_stats(const uint8_t* __restrict_
   for (size_t i = n16 * 16 + (size_t)blockIdx.x * NT + t; i < n; i += (size_t)gridDim.x * NT)
     if (select[i]) surf_visit<MODE>(select, dist, i, d, hb, acc, shist);
   sm[t] = acc;
-  surf_block_tree(sm);
+  pp_block_tree<NT>(t, [&](int a, int b) { surf_merge(sm[a], sm[b]); });
   if (t == 0) partials[blockIdx.x] = sm[0];
   if (hb.on && t < CMP_BINS && shist[t]) atomicAdd(&hist[t], (unsigned long long)shist[t]);
 }
@@ -232,7 +182,7 @@ __global__ void __launch_bounds__(NT) k_surface_final(const surf_acc* __restrict
   surf_acc acc{0ull, 0ull, 0.0, 0.0, FLT_MAX, -FLT_MAX};
   for (int b = t; b < nb; b += NT) surf_merge(acc, partials[b]);
   sm[t] = acc;
-  surf_block_tree(sm);
+  pp_block_tree<NT>(t, [&](int a, int b) { surf_merge(sm[a], sm[b]); });
   if (t == 0) {
     out->count = (int64_t)sm[0].count;
     out->count_le_tau = (int64_t)sm[0].cle;
@@ -265,11 +215,7 @@ __global__ void __launch_bounds__(NT) k_slice_masked_count(const uint8_t* __rest
     }
   }
   red[t] = cnt;
-  __syncthreads();
-  for (int s = NT / 2; s > 0; s >>= 1) {
-    if (t < s) red[t] += red[t + s];
-    __syncthreads();
-  }
+  pp_block_tree<NT>(t, [&](int a, int b) { red[a] += red[b]; });
   if (t == 0 && red[0]) atomicAdd(&per_slice[z], (unsigned long long)red[0]);
 }
 
@@ -330,8 +276,8 @@ int pp_abs_range_f32(pp_ctx* ctx, const float* in, size_t n, float* device_range
   float* partials = reinterpret_cast<float*>(ctx->ws);
   hipLaunchKernelGGL(k_abs_range_partial, dim3(nb), dim3(NT), 0, ctx->stream, in, n, partials);
   PP_LAUNCH_CHECK(ctx, "k_abs_range_partial");
-  hipLaunchKernelGGL(k_abs_range_final, dim3(1), dim3(NT), 0, ctx->stream, (const float*)partials, (int)nb, device_range);
-  PP_LAUNCH_CHECK(ctx, "k_abs_range_final");
+  hipLaunchKernelGGL((k_range_fold<NT, float>), dim3(1), dim3(NT), 0, ctx->stream, (const float*)partials, (int)nb, device_range);
+  PP_LAUNCH_CHECK(ctx, "k_range_fold");
   return PP_OK;
 }
 

@@ -37,6 +37,8 @@
 // 2^-24 fixed point, the counts in 64-bit integers: the statistics are bit-reproducible too.
 #pragma once
 
+#include "pp_reduce.h"
+
 namespace {
 
 constexpr int FI_MAX_ITERATIONS = 256;           // rows of the per-iteration table
@@ -103,14 +105,10 @@ __device__ __forceinline__ void fi_block_reduce(int& mx, unsigned long long& sm,
   const int t = threadIdx.y * blockDim.x + threadIdx.x;
   smx[t] = mx;
   ssm[t] = sm;
-  __syncthreads();
-  for (int s = NT / 2; s > 0; s >>= 1) {
-    if (t < s) {
-      smx[t] = smx[t] > smx[t + s] ? smx[t] : smx[t + s];
-      ssm[t] += ssm[t + s];
-    }
-    __syncthreads();
-  }
+  pp_block_tree<NT>(t, [=](int a, int b) {
+    smx[a] = smx[a] > smx[b] ? smx[a] : smx[b];
+    ssm[a] += ssm[b];
+  });
   mx = smx[0];
   sm = ssm[0];
 }
@@ -393,17 +391,13 @@ __global__ void __launch_bounds__(NT) k_jacobian_det(const float* __restrict__ u
     s_sum[t] = (unsigned long long)lsum;
     s_cnt[t] = lcnt;
     s_np[t] = lnp;
-    __syncthreads();
-    for (int s = NT / 2; s > 0; s >>= 1) {
-      if (t < s) {
-        s_min[t] = s_min[t] < s_min[t + s] ? s_min[t] : s_min[t + s];
-        s_max[t] = s_max[t] > s_max[t + s] ? s_max[t] : s_max[t + s];
-        s_sum[t] += s_sum[t + s];
-        s_cnt[t] += s_cnt[t + s];
-        s_np[t] += s_np[t + s];
-      }
-      __syncthreads();
-    }
+    pp_block_tree<NT>(t, [&](int a, int b) {
+      s_min[a] = s_min[a] < s_min[b] ? s_min[a] : s_min[b];
+      s_max[a] = s_max[a] > s_max[b] ? s_max[a] : s_max[b];
+      s_sum[a] += s_sum[b];
+      s_cnt[a] += s_cnt[b];
+      s_np[a] += s_np[b];
+    });
     if (t == 0 && s_cnt[0]) {
       atomicMin(&acc->min_key, s_min[0]);
       atomicMax(&acc->max_key, s_max[0]);

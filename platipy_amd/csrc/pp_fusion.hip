@@ -11,6 +11,7 @@
 
 #include "pp_internal.h"
 #include "pp_kernels.h"
+#include "pp_reduce.h"
 
 namespace {
 
@@ -180,50 +181,13 @@ __global__ void __launch_bounds__(NT) k_sum_final(const double* __restrict__ par
 }
 
 __global__ void __launch_bounds__(NT) k_minmax_partial(const float* __restrict__ in, size_t n, float* __restrict__ partials) {
-  __shared__ float smin[NT], smax[NT];
   float lo = FLT_MAX, hi = -FLT_MAX;
   for (size_t i = (size_t)blockIdx.x * NT + threadIdx.x; i < n; i += (size_t)gridDim.x * NT) {
     const float v = in[i];
     lo = fminf(lo, v);
     hi = fmaxf(hi, v);
   }
-  smin[threadIdx.x] = lo;
-  smax[threadIdx.x] = hi;
-  __syncthreads();
-  for (int s = NT / 2; s > 0; s >>= 1) {
-    if ((int)threadIdx.x < s) {
-      smin[threadIdx.x] = fminf(smin[threadIdx.x], smin[threadIdx.x + s]);
-      smax[threadIdx.x] = fmaxf(smax[threadIdx.x], smax[threadIdx.x + s]);
-    }
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) {
-    partials[2 * blockIdx.x] = smin[0];
-    partials[2 * blockIdx.x + 1] = smax[0];
-  }
-}
-
-__global__ void __launch_bounds__(NT) k_minmax_final(const float* __restrict__ partials, int count, float* __restrict__ result) {
-  __shared__ float smin[NT], smax[NT];
-  float lo = FLT_MAX, hi = -FLT_MAX;
-  for (int i = threadIdx.x; i < count; i += NT) {
-    lo = fminf(lo, partials[2 * i]);
-    hi = fmaxf(hi, partials[2 * i + 1]);
-  }
-  smin[threadIdx.x] = lo;
-  smax[threadIdx.x] = hi;
-  __syncthreads();
-  for (int s = NT / 2; s > 0; s >>= 1) {
-    if ((int)threadIdx.x < s) {
-      smin[threadIdx.x] = fminf(smin[threadIdx.x], smin[threadIdx.x + s]);
-      smax[threadIdx.x] = fmaxf(smax[threadIdx.x], smax[threadIdx.x + s]);
-    }
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) {
-    result[0] = smin[0];
-    result[1] = smax[0];
-  }
+  pp_block_range_store<NT>(lo, hi, partials + 2 * (size_t)blockIdx.x);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -302,12 +266,9 @@ __global__ void __launch_bounds__(NT) k_sum14_final(const double* __restrict__ p
   for (int i = threadIdx.x; i < count; i += NT)
     for (int f = 0; f < nf; ++f) acc[f] += partials[(size_t)i * row + f0 + f];
   for (int f = 0; f < 14; ++f) red[f * NT + threadIdx.x] = acc[f];
-  __syncthreads();
-  for (int s = NT / 2; s > 0; s >>= 1) {
-    if ((int)threadIdx.x < s)
-      for (int f = 0; f < 14; ++f) red[f * NT + threadIdx.x] += red[f * NT + threadIdx.x + s];
-    __syncthreads();
-  }
+  pp_block_tree<NT>((int)threadIdx.x, [&](int a, int b) {
+    for (int f = 0; f < 14; ++f) red[f * NT + a] += red[f * NT + b];
+  });
   if ((int)threadIdx.x < nf) {
     if (to_mailbox)   // `result` is the host mailbox: block b is writer b, field f its entry f (pp_internal.h)
       pp_mail_post(pp_mail_slot(result, (int)blockIdx.x) + threadIdx.x, red[threadIdx.x * NT], seq);
@@ -1234,8 +1195,8 @@ int pp_minmax_f32(pp_ctx* ctx, const float* in, size_t n, float* min_out, float*
   float* partials = reinterpret_cast<float*>(ctx->ws);
   hipLaunchKernelGGL(k_minmax_partial, dim3(nb), dim3(NT), 0, ctx->stream, in, n, partials);
   PP_LAUNCH_CHECK(ctx, "k_minmax_partial");
-  hipLaunchKernelGGL(k_minmax_final, dim3(1), dim3(NT), 0, ctx->stream, (const float*)partials, (int)nb, partials + 2 * nb);
-  PP_LAUNCH_CHECK(ctx, "k_minmax_final");
+  hipLaunchKernelGGL((k_range_fold<NT, float>), dim3(1), dim3(NT), 0, ctx->stream, (const float*)partials, (int)nb, partials + 2 * nb);
+  PP_LAUNCH_CHECK(ctx, "k_range_fold");
   float h[2];
   rc = pp_read_back(ctx, partials + 2 * nb, h, sizeof(h));
   if (rc) return rc;

@@ -5,6 +5,8 @@
 // 331-339).  Integer atomics only: every result is independent of the order in which blocks run.
 #include <vector>
 
+#include "pp_reduce.h"
+
 namespace {
 
 constexpr int RG_E = 16;                 // voxels per thread of the scan and moment kernels
@@ -24,11 +26,7 @@ __global__ void __launch_bounds__(NT) k_rg_root_count(const uint8_t* __restrict_
     for (int e = 0; e < RG_E; ++e)
       if (i0 + e < n) cnt += rg_is_root(mask, L, i0 + e);
     s[threadIdx.x] = cnt;
-    __syncthreads();
-    for (int h = NT / 2; h > 0; h >>= 1) {
-      if ((int)threadIdx.x < h) s[threadIdx.x] += s[threadIdx.x + h];
-      __syncthreads();
-    }
+    pp_block_tree<NT>((int)threadIdx.x, [&](int a, int b) { s[a] += s[b]; });
     if (threadIdx.x == 0) chunk_count[c] = s[0];
     __syncthreads();
   }
@@ -226,11 +224,7 @@ __global__ void __launch_bounds__(NT) k_rg_select(const uint8_t* __restrict__ ma
     cnt += in;
   }
   s[threadIdx.x] = cnt;
-  __syncthreads();
-  for (int h = NT / 2; h > 0; h >>= 1) {
-    if ((int)threadIdx.x < h) s[threadIdx.x] += s[threadIdx.x + h];
-    __syncthreads();
-  }
+  pp_block_tree<NT>((int)threadIdx.x, [&](int a, int b) { s[a] += s[b]; });
   if (threadIdx.x == 0 && s[0]) atomicAdd(voxels, (unsigned long long)s[0]);
 }
 

@@ -14,6 +14,8 @@
 // the 1e-14 stopping test needs.  No float atomics.
 #pragma once
 
+#include "pp_reduce.h"
+
 namespace {
 
 constexpr int ST_MAX_R = PP_STAPLE_MAX_RATERS;
@@ -101,12 +103,9 @@ __global__ void __launch_bounds__(NT) k_staple_pack(staple_inputs in, int R, siz
   }
   const int t = threadIdx.x;
   red[0][t] = c0; red[1][t] = c1; red[2][t] = cm; red[3][t] = pc;
-  __syncthreads();
-  for (int s = NT / 2; s > 0; s >>= 1) {
-    if (t < s)
-      for (int f = 0; f < 4; ++f) red[f][t] += red[f][t + s];
-    __syncthreads();
-  }
+  pp_block_tree<NT>(t, [&](int a, int b) {
+    for (int f = 0; f < 4; ++f) red[f][a] += red[f][b];
+  });
   if (t < 4) counts[4 * (size_t)blockIdx.x + t] = red[t][0];
 }
 
@@ -236,52 +235,13 @@ __global__ void __launch_bounds__(ST_FOLD_NT) k_staple_fold(const double* __rest
 // min / max of W over the mixed keys: partials[2 b] = min, [2 b + 1] = max (+-inf for a block without keys)
 __global__ void __launch_bounds__(NT) k_staple_wminmax(const unsigned long long* __restrict__ mixed, size_t m, staple_model md,
                                                        double* __restrict__ partials) {
-  __shared__ double smin[NT], smax[NT];
   double lo = INFINITY, hi = -INFINITY;
   for (size_t i = (size_t)blockIdx.x * NT + threadIdx.x; i < m; i += (size_t)gridDim.x * NT) {
     const double w = st_weight(mixed[i], md);
     lo = fmin(lo, w);
     hi = fmax(hi, w);
   }
-  const int t = threadIdx.x;
-  smin[t] = lo;
-  smax[t] = hi;
-  __syncthreads();
-  for (int s = NT / 2; s > 0; s >>= 1) {
-    if (t < s) {
-      smin[t] = fmin(smin[t], smin[t + s]);
-      smax[t] = fmax(smax[t], smax[t + s]);
-    }
-    __syncthreads();
-  }
-  if (t == 0) {
-    partials[2 * (size_t)blockIdx.x] = smin[0];
-    partials[2 * (size_t)blockIdx.x + 1] = smax[0];
-  }
-}
-
-__global__ void __launch_bounds__(NT) k_staple_minmax_final(const double* __restrict__ partials, int nb, double* __restrict__ result) {
-  __shared__ double smin[NT], smax[NT];
-  double lo = INFINITY, hi = -INFINITY;
-  for (int b = threadIdx.x; b < nb; b += NT) {
-    lo = fmin(lo, partials[2 * b]);
-    hi = fmax(hi, partials[2 * b + 1]);
-  }
-  const int t = threadIdx.x;
-  smin[t] = lo;
-  smax[t] = hi;
-  __syncthreads();
-  for (int s = NT / 2; s > 0; s >>= 1) {
-    if (t < s) {
-      smin[t] = fmin(smin[t], smin[t + s]);
-      smax[t] = fmax(smax[t], smax[t + s]);
-    }
-    __syncthreads();
-  }
-  if (t == 0) {
-    result[0] = smin[0];
-    result[1] = smax[0];
-  }
+  pp_block_range_store<NT>(lo, hi, partials + 2 * (size_t)blockIdx.x);
 }
 
 // W per voxel from its key; with `rescale`: RescaleIntensity(0, 1) (x * scale + shift, clamped) then Threshold(lower, 1, 0).
@@ -464,8 +424,8 @@ extern "C" int pp_staple_fuse(pp_ctx* ctx, const void* const* labels, int dtype,
     if (nm > 0) {
       hipLaunchKernelGGL(k_staple_wminmax, dim3(nbm), dim3(NT), 0, ctx->stream, (const unsigned long long*)mixed, (size_t)nm, md, mm_part);
       PP_LAUNCH_CHECK(ctx, "k_staple_wminmax");
-      hipLaunchKernelGGL(k_staple_minmax_final, dim3(1), dim3(NT), 0, ctx->stream, (const double*)mm_part, (int)nbm, mm_part + 2 * (size_t)nbm);
-      PP_LAUNCH_CHECK(ctx, "k_staple_minmax_final");
+      hipLaunchKernelGGL((k_range_fold<NT, double>), dim3(1), dim3(NT), 0, ctx->stream, (const double*)mm_part, (int)nbm, mm_part + 2 * (size_t)nbm);
+      PP_LAUNCH_CHECK(ctx, "k_range_fold");
       double mm[2];
       rc = pp_read_back(ctx, mm_part + 2 * (size_t)nbm, mm, sizeof(mm));
       if (rc) return rc;

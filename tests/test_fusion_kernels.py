@@ -1,5 +1,5 @@
 """The label-fusion map and reduction kernels at the head of pp_fusion.hip (k_map4<Op> with its seven functors, k_ssd_partial /
-k_sum_final, k_minmax_partial / k_minmax_final) at the C ABI against the numpy / fp64 restatements of
+k_sum_final, k_minmax_partial / k_range_fold<float>) at the C ABI against the numpy / fp64 restatements of
 tests/fusion_restatement.py, on every arm ("Fusion arithmetic, which call enters which arm of k_map4"):
 
   sizes       N_EDGE: n < 4, n % 4 = 0 .. 3, one voxel either side of a block (256) and of a block of 16-byte quads (1024);
