@@ -653,6 +653,32 @@ typedef struct {
 } pp_contour;
 int pp_contour_fill_u8(pp_ctx* ctx, const int32_t* vertices, int nverts, const pp_contour* contours, int ncontours,
                        const int size[3], int nstructures, uint8_t* out);
+/* Binary masks to closed planar contours, the inverse of pp_contour_fill_u8 and the volume-sized step of
+ * dicom/io/nifti_to_rtstruct.py (convert_nifti, which hands every mask to rt-utils and OpenCV on the host), for all structures
+ * and all slices in ONE extraction.  masks: DEVICE, uint8 [nstructures][size[2]][size[1]][size[0]], foreground = any non-zero
+ * byte.  The rule (T1-T7 of platipy_amd/dicom, csrc/pp_contour_trace.h): the boundary of a slice is cut into directed cracks
+ * (pixel sides with the foreground on their right as displayed), 8-connected foreground, linked into loops; a loop's leader is
+ * its crack with the smallest (y, x, side); a leader on a north side is an outer border (clockwise as displayed), on a south
+ * side a hole (the other way round).  A contour's vertices are the pixels the loop runs through -- its own foreground pixels
+ * for an outer border, the hole's own background pixels for a hole -- every border pixel once per visit, starting at the
+ * leader's pixel; with approximate != 0 a vertex whose incoming and outgoing steps are equal is dropped (lossy on parts one
+ * pixel wide).  Contours are ordered by (structure, z, leader).  With approximate == 0, pp_contour_fill_u8 of the result gives
+ * `masks` back byte for byte (as 0 / 1).  Parity with rt-utils / OpenCV is UNPINNED (neither is installed where this is
+ * tested).
+ *   Call shape: a COUNT call (vertices == contours == hole == NULL, nverts == ncontours == 0) runs the extraction, leaves the
+ * tables in the context's scratch and writes counts = {cracks, vertices, contours} (HOST).  A FILL call (vertices: HOST,
+ * nverts x 2 int32 (x, y); contours: HOST, ncontours rows {first, count, structure, z}; hole: HOST, ncontours bytes, 1 for a
+ * hole) with exactly those counts copies them out.  A fill call that directly follows the count call of the same arguments on
+ * the same context -- no other library call on it in between, `masks` unchanged -- only copies; any other fill call runs the
+ * extraction first.  An extraction makes two host read-backs ({cracks, cracks of the largest slice}; {vertices, contours}).
+ * Integer arithmetic only, one integer atomicMax, every output word written by one thread: reruns are bit-identical.  No
+ * workgroup waits for another: every pointer-doubling round is its own launch, ceil(log2(cracks of the largest slice)) + 1
+ * rounds for the leaders and as many for the ranking.  Scratch: one int per row and 64-pixel block, about 50 bytes per crack.
+ * PP_ERR_ARG for a NULL argument, a NULL table beside a non-zero count, a negative count, table counts that are not the
+ * extraction's (counts is still written), nstructures < 1, an empty volume, more than 2^31 - 1 cracks; an axis longer than
+ * 2^24 or more than 2^31 - 1 rows: PP_ERR_SIZE.  Synchronises. */
+int pp_contour_trace_u8(pp_ctx* ctx, const uint8_t* masks, const int size[3], int nstructures, int approximate,
+                        int32_t* vertices, int nverts, pp_contour* contours, uint8_t* hole, int ncontours, int64_t counts[3]);
 
 /* ---- region primitives (airway and lung segmentation) ------------------------------- */
 /* sitk.ConnectedComponent(mask) with face connectivity (imaging/utils/lung.py:41-42, projects/bronchus/bronchus.py:214 and

@@ -246,6 +246,7 @@ _SIGNATURES = {
     "pp_tube_mask_u8": (C.c_int, [_P, C.POINTER(C.c_double), C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_double), C.POINTER(C.c_double),
                                   C.c_double, _P]),
     "pp_contour_fill_u8": (C.c_int, [_P, _P, C.c_int, _P, C.c_int, C.POINTER(C.c_int), C.c_int, _P]),
+    "pp_contour_trace_u8": (C.c_int, [_P, _P, C.POINTER(C.c_int), C.c_int, C.c_int, _P, C.c_int, _P, _P, C.c_int, C.POINTER(C.c_int64)]),
     "pp_connected_components_u8": (C.c_int, [_P, _P, C.POINTER(C.c_int), _P, C.POINTER(C.c_int)]),
     "pp_connected_components_conn_u8": (C.c_int, [_P, _P, C.POINTER(C.c_int), C.c_int, _P, C.POINTER(C.c_int)]),
     "pp_slice_convex_hull_u8": (C.c_int, [_P, _P, C.POINTER(C.c_int), _P]),
@@ -776,6 +777,30 @@ class Context:
         self._chk_value(self.lib.pp_contour_fill_u8(self.h, v.ctypes.data if v.size else None, int(v.shape[0]),
                                                     ct.ctypes.data if ct.size else None, int(ct.size), _i3(size), int(nstructures), ptr(out)),
                         "pp_contour_fill_u8")
+
+    def contour_trace(self, masks, size, nstructures, approximate=False, with_cracks=False):
+        """pp_contour_trace_u8: the closed contours of the uint8 masks [nstructures][Z][Y][X] (device memory, foreground = any
+        non-zero byte) -> (vertices int32 [n, 2] of (x, y), CONTOUR_DTYPE rows, hole flags uint8), all host arrays, the rows
+        ordered by (structure, z, leader) -- what contour_fill takes.  One count call and one fill call of the library: the
+        extraction runs once (two read-backs), the second call copies.  with_cracks=True appends the crack count.
+        ValueError for a buffer that does not hold nstructures volumes, nstructures < 1, more than 2^31 - 1 cracks.
+        Synchronises."""
+        _check_volume("contour_trace", size)
+        have = _nbytes(masks)
+        if int(nstructures) < 1:
+            raise ValueError("contour_trace: at least one structure")
+        if have is not None and have != int(nstructures) * int(size[0]) * int(size[1]) * int(size[2]):
+            raise ValueError(f"contour_trace: `masks` does not hold {nstructures} volumes of {tuple(size)} ({have} bytes)")
+        counts = (C.c_int64 * 3)()
+        self._chk_value(self.lib.pp_contour_trace_u8(self.h, ptr(masks), _i3(size), int(nstructures), int(bool(approximate)), None, 0,
+                                                     None, None, 0, counts), "pp_contour_trace_u8")
+        nv, nc = int(counts[1]), int(counts[2])
+        verts, rows, hole = np.empty((nv, 2), dtype=np.int32), np.empty(nc, dtype=CONTOUR_DTYPE), np.empty(nc, dtype=np.uint8)
+        if nc:
+            self._chk_value(self.lib.pp_contour_trace_u8(self.h, ptr(masks), _i3(size), int(nstructures), int(bool(approximate)),
+                                                         verts.ctypes.data, nv, rows.ctypes.data, hole.ctypes.data, nc, counts),
+                            "pp_contour_trace_u8")
+        return (verts, rows, hole, int(counts[0])) if with_cracks else (verts, rows, hole)
 
     # -- region primitives ------------------------------------------------------------
     def connected_components(self, mask, size, labels, want_count=True):

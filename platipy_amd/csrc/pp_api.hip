@@ -155,6 +155,7 @@ extern "C" void pp_reload_switches(void) {
 }
 
 int pp_reserve(pp_ctx* ctx, size_t bytes) {
+  ctx->trace.valid = 0;   // (whoever reserves the scratch writes it)
   if (bytes <= ctx->ws_bytes) {
     // debugging aid: PP_POISON_WS=1 fills the reserved scratch with NaN bytes on every call, so a kernel that reads
     // scratch it did not write shows up as NaN / changed results (tools/stress_streams.py)

@@ -1541,3 +1541,6 @@ int pp_linear_set_sample_jitter(pp_ctx* ctx, const float* jitter, size_t nsample
 
 // RTSTRUCT contours to masks (dicom/io/rtstruct_to_nifti.py): pp_contour_fill_u8
 #include "pp_contour.h"
+
+// masks to RTSTRUCT contours (dicom/io/nifti_to_rtstruct.py): pp_contour_trace_u8
+#include "pp_contour_trace.h"

@@ -56,6 +56,15 @@ struct pp_ctx {
   // ... and its packed companion (pp_linear_set_moving_gradient_packed): (gx, gy, gz, intensity) per voxel of the SAME moving image,
   // what the value + gradient kernel gathers from when it is set (a quarter of the cache sectors per sample)
   const float* mgrad4;
+  // The last extraction of pp_contour_trace_u8, whose tables stay in `ws` between its count call and its fill call: the
+  // arguments it was made for and where the tables lie.  pp_reserve clears `valid`: any other use of the scratch ends it.
+  struct {
+    int valid;
+    const unsigned char* masks;
+    int size[3], nstructures, approximate;
+    long long cracks, verts, contours;
+    size_t off_verts, off_rows, off_holes;
+  } trace;
   char err[512];
 };
 

@@ -1,4 +1,5 @@
-"""RTSTRUCT contours to binary masks on the GPU (platipy/dicom/io/rtstruct_to_nifti.py:54-217; csrc/pp_contour.h).
+"""RTSTRUCT contours to binary masks on the GPU (platipy/dicom/io/rtstruct_to_nifti.py:54-217; csrc/pp_contour.h), and binary
+masks back to RTSTRUCT contours (platipy/dicom/io/nifti_to_rtstruct.py; csrc/pp_contour_trace.h; T1-T7 below).
 
 The reference loops over structures and contours, calls skimage.draw.polygon for each contour and XORs the result into a
 slice.  Here the vertices of ALL structures are transformed to indices in one vectorised fp64 step on the host and all
@@ -39,6 +40,35 @@ What is kept of the reference, and what is not:
   R11  fix_missing_data: one empty string in ContourData is repaired, x or y from the two neighbouring vertices of the
        closed contour, z from the other vertices.  The reference's own arithmetic there runs on an array of strings and its
        wrap-around for the last y reads past the end; this is the behaviour it describes, not its text.
+
+Masks to contours.  The reference (nifti_to_rtstruct.py, convert_nifti) hands each mask to rt-utils, which traces it slice by
+slice with OpenCV's findContours on the host; neither is installed where this is tested and parity with them is UNPINNED.
+Here ONE extraction of pp_contour_trace_u8 traces all structures and slices, by these rules, chosen so that R3's fill of the
+result gives the masks back byte for byte.  The deliberate differences to rt-utils / OpenCV: every border pixel is a vertex
+(approximate_contours is off by default), hole contours run through the hole's own pixels so that the XOR of R5 restores the
+mask, and no pinholes are cut to join a hole to its outer contour.
+  T1   per structure and slice; a pixel is (x, y), x to the right, y down; foreground is any non-zero value.  A foreground
+       pixel has a CRACK on each side (N, E, S, W) whose 4-neighbour is background or outside the slice.  A crack is directed
+       with its own pixel on its right as displayed: N heads east, E south, S west, W north.
+  T2   foreground is 8-connected, background 4-connected.  At a crack's head corner, with AL / AR the pixels ahead-left /
+       ahead-right (outside the slice = background): AL foreground -> the crack of AL (left turn); else AR foreground -> the
+       crack of AR (straight on); else the next side of the same pixel (right turn).  Every crack has one successor and one
+       predecessor: the cracks form disjoint cycles, the LOOPS.
+  T3   a loop's LEADER is its crack with the smallest key (y, x, side), N < E < S < W.  A leader on side N: the outer border of
+       an 8-connected component; on side S: the border of a hole (a 4-connected background component that does not reach
+       the slice's edge).  (The test restatement decides this by the sign of the enclosed area instead.)
+  T4   the SIDE PIXEL of a crack is its own pixel on an outer loop, the background pixel across the crack on a hole loop.
+  T5   walking a loop from its leader, each maximal cyclic run of equal side pixels is one vertex; the first vertex is the run
+       that holds the leader, even when that run began before it; outer borders run clockwise as displayed, holes the other
+       way; a single pixel gives one vertex; consecutive vertices are 8-adjacent; no vertex is dropped.
+  T6   contours are ordered by (structure, z, leader key); vertices are int32 (x, y), rows {first, count, structure, z} as
+       pp_contour_fill_u8 takes them, and a parallel uint8 array flags the holes.
+  T7   approximate_contours=True (rt-utils' CHAIN_APPROX_SIMPLE): from a contour of more than two vertices every vertex whose
+       incoming step equals its outgoing step is dropped (cyclic neighbours, all decided on the full sequence) and the contour
+       starts at the first kept vertex at or after the T5 start.  LOSSY on parts one pixel wide: the spur a b c b a becomes
+       a c a and R3 no longer sees b, so the fill of the result may miss pixels of the mask.
+  T8   ROIDisplayColor: the reference colours a structure by hash(name) % 256, which differs from run to run; here a fixed
+       palette indexed by the structure's position, or the caller's colours (deviation).
 """
 import logging
 
@@ -50,7 +80,7 @@ from ..image import Image, as_image
 
 logger = logging.getLogger(__name__)
 
-__all__ = ["fix_missing_data", "rasterise_contours", "transform_point_set_from_dicom_struct"]
+__all__ = ["contours_to_dicom_struct", "extract_contours", "fix_missing_data", "rasterise_contours", "transform_point_set_from_dicom_struct"]
 
 
 def fix_missing_data(contour_data):
@@ -181,3 +211,70 @@ def transform_point_set_from_dicom_struct(dicom_image, dicom_struct, spacing_ove
         structures.append((name, [np.array(fix_missing_data(c.ContourData), dtype=np.float64).reshape(-1, 3) for c in sequence]))
     out, names, spacing = _rasterise(ref, structures, spacing_override)
     return [Image(out[k], spacing, ref.GetOrigin(), ref.GetDirection()) for k in range(len(names))], names
+
+
+def extract_contours(masks, approximate_contours=False, as_physical=True):
+    """Closed planar contours of binary masks, the inverse of rasterise_contours (T1-T7).  masks: {name: Image}, scalar images
+    on ONE grid (ValueError otherwise), foreground = any non-zero voxel.  -> {name: [points, ...]} in insertion order, every
+    `points` a float64 [n, 3] array of physical points in mm, origin + direction diag(spacing) (x, y, z), one closed contour;
+    within a structure the contours keep the order of T6 (slice, then leader); a structure without foreground maps to [].
+    as_physical=False -> (int32 vertices [n, 2] of (x, y), CONTOUR_DTYPE rows, uint8 hole flags, names): the tables
+    Context.contour_fill takes.  All structures and slices are traced by one extraction of pp_contour_trace_u8; with
+    approximate_contours=False rasterise_contours of the result on the same grid gives the masks back."""
+    names = list(masks)
+    images = [as_image(masks[n]) for n in names]
+    for name, img in zip(names, images):
+        if img.is_vector:
+            raise ValueError(f"extract_contours: {name} is a vector image")
+        if not img.same_grid(images[0]):
+            raise ValueError(f"extract_contours: {name} is not on the grid of {names[0]}")
+    if not names:
+        empty = np.zeros((0, 2), np.int32), np.zeros(0, _lib.CONTOUR_DTYPE), np.zeros(0, np.uint8), []
+        return {} if as_physical else empty
+    ref = images[0]
+    nx, ny, nz = ref.GetSize()
+    stack = torch.stack([i.tensor if i.tensor.dtype == torch.uint8 else (i.tensor != 0).to(torch.uint8) for i in images]).contiguous()
+    verts, rows, hole = runtime.context(ref.device).contour_trace(stack, (nx, ny, nz), len(names), approximate_contours)
+    if not as_physical:
+        return verts, rows, hole, names
+    index = np.empty((verts.shape[0], 3), dtype=np.float64)
+    index[:, :2] = verts
+    index[:, 2] = np.repeat(rows["z"], rows["count"])
+    m = np.asarray(ref.GetDirection(), dtype=np.float64).reshape(3, 3) @ np.diag(np.asarray(ref.GetSpacing(), dtype=np.float64))
+    points = index @ m.T + np.asarray(ref.GetOrigin(), dtype=np.float64)
+    out = {name: [] for name in names}
+    for first, count, s, _ in rows.tolist():
+        out[names[s]].append(points[first:first + count])
+    return out
+
+
+# ROIDisplayColor by position (T8)
+PALETTE = ((255, 0, 0), (0, 255, 0), (0, 0, 255), (255, 255, 0), (0, 255, 255), (255, 0, 255), (255, 128, 0), (128, 255, 0),
+           (0, 255, 128), (0, 128, 255), (128, 0, 255), (255, 0, 128), (255, 128, 128), (128, 255, 128), (128, 128, 255), (192, 192, 192))
+
+
+def contours_to_dicom_struct(contours, colours=None):
+    """{name: [points [n, 3] in mm, ...]} (what extract_contours returns) -> a tree of types.SimpleNamespace with the attributes
+    of an RTSTRUCT that transform_point_set_from_dicom_struct reads -- StructureSetROISequence[*].ROINumber / .ROIName and
+    ROIContourSequence[*].ReferencedROINumber / .ContourSequence[*].ContourGeometricType ("CLOSED_PLANAR") / .ContourData
+    (flat x0, y0, z0, x1, ...) -- plus NumberOfContourPoints and ROIDisplayColor.  ROI numbers count from 1 in insertion
+    order.  colours: {name: (r, g, b)} or a sequence by position; otherwise PALETTE by position (T8).  A user with pydicom
+    copies these fields into a Dataset; writing files is not part of this module."""
+    from types import SimpleNamespace
+
+    rois, sequence = [], []
+    for k, (name, polys) in enumerate(contours.items()):
+        if colours is None:
+            colour = PALETTE[k % len(PALETTE)]
+        else:
+            colour = colours[name] if isinstance(colours, dict) else colours[k]
+        items = []
+        for points in polys:
+            p = np.asarray(points, dtype=np.float64)
+            if p.ndim != 2 or p.shape[1] != 3 or p.shape[0] < 1:
+                raise ValueError(f"a contour is an [n, 3] array of points with n >= 1, got shape {p.shape}")
+            items.append(SimpleNamespace(ContourGeometricType="CLOSED_PLANAR", NumberOfContourPoints=int(p.shape[0]),
+                                         ContourData=p.ravel().tolist()))
+        rois.append(SimpleNamespace(ROINumber=k + 1, ROIName=str(name)))
+        sequence.append(SimpleNamespace(ReferencedROINumber=k + 1, ROIDisplayColor=[int(c) for c in colour], ContourSequence=items))
+    return SimpleNamespace(StructureSetROISequence=rois, ROIContourSequence=sequence)
