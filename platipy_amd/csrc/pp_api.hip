@@ -156,10 +156,10 @@ extern "C" void pp_reload_switches(void) {
 
 int pp_reserve(pp_ctx* ctx, size_t bytes) {
   ctx->trace.valid = 0;   // (whoever reserves the scratch writes it)
+  // debugging aid: PP_POISON_WS=1 fills the reserved scratch with NaN bytes on every call, so a kernel that reads
+  // scratch it did not write shows up as NaN / changed results (tools/stress_streams.py, tests/test_memory_state.py)
+  const bool poison = pp_env("PP_POISON_WS") != nullptr;
   if (bytes <= ctx->ws_bytes) {
-    // debugging aid: PP_POISON_WS=1 fills the reserved scratch with NaN bytes on every call, so a kernel that reads
-    // scratch it did not write shows up as NaN / changed results (tools/stress_streams.py)
-    const bool poison = pp_env("PP_POISON_WS") != nullptr;
     if (poison && bytes) PP_HIP(ctx, hipMemsetAsync(ctx->ws, 0xFF, bytes, ctx->stream));
     return PP_OK;
   }
@@ -178,6 +178,8 @@ int pp_reserve(pp_ctx* ctx, size_t bytes) {
   }
   ctx->ws = static_cast<char*>(p);
   ctx->ws_bytes = want;
+  // a growth is the first call at every size: the fresh allocation is poisoned as a whole, not only `bytes` of it
+  if (poison) PP_HIP(ctx, hipMemsetAsync(ctx->ws, 0xFF, want, ctx->stream));
   return PP_OK;
 }
 

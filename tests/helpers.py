@@ -31,6 +31,20 @@ class EmuBackend:
     def empty(self, shape, dtype=np.float32):
         return np.zeros(shape, dtype=dtype)
 
+    def garbage(self, shape, dtype, pattern):
+        return host_garbage(shape, dtype, pattern)
+
+
+def host_garbage(shape, dtype, pattern):
+    """A numpy buffer that holds what a call must overwrite.  pattern: an int 0 .. 255 puts it into every BYTE (0xFF is a NaN
+    in every float type), a float into every ELEMENT."""
+    dt = np.dtype(dtype)
+    shape = (shape,) if np.isscalar(shape) else tuple(shape)
+    if isinstance(pattern, (int, np.integer)):
+        n = int(np.prod(shape, dtype=np.int64)) * dt.itemsize
+        return np.full(n, int(pattern), np.uint8).view(dt).reshape(shape)
+    return np.full(shape, pattern, dtype=dt)
+
 
 class GpuBackend:
     """The real libplatipy_hip.so on cuda:0; buffers are torch tensors."""
@@ -55,6 +69,18 @@ class GpuBackend:
     def empty(self, shape, dtype=np.float32):
         tdt = {np.float32: self.torch.float32, np.uint8: self.torch.uint8}[dtype]
         return self.torch.zeros(tuple(shape), dtype=tdt, device="cuda")
+
+    def garbage(self, shape, dtype, pattern):
+        """host_garbage on the device.  torch has no unsigned 32-bit tensors here: a uint32 buffer comes back as int32 (the
+        same bytes; view it as uint32 on the host)."""
+        t = self.torch
+        dt = np.dtype(dtype)
+        tdt = {"float32": t.float32, "float64": t.float64, "uint8": t.uint8, "int32": t.int32, "uint32": t.int32, "int64": t.int64}[dt.name]
+        shape = (shape,) if np.isscalar(shape) else tuple(shape)
+        if isinstance(pattern, (int, np.integer)):
+            n = int(np.prod(shape, dtype=np.int64)) * dt.itemsize
+            return t.full((n,), int(pattern), dtype=t.uint8, device="cuda").view(tdt).reshape(shape)
+        return t.full(shape, pattern, dtype=tdt, device="cuda")
 
 
 # --------------------------------------------------------------------------------------

@@ -170,7 +170,7 @@ def test_tube_mask_odd_volumes(backend, shape):
     bricks), and a volume smaller than one brick."""
     nz, ny, nx = shape
     line = [p(0.6, 0.7, 0.2), p(nx * 0.55, ny * 0.35, nz * 0.6), p(nx - 1.3, ny - 1.6, nz - 1.2)]
-    check_tube(backend, line, 1.7)
+    check_tube(backend, line, 1.7, shape=shape)
 
 
 def test_tube_mask_flat_ends(backend):
