@@ -185,6 +185,31 @@ int pp_resample_u8(pp_ctx* ctx, const uint8_t* in, const pp_geom* gin, const pp_
 int pp_resample_set(pp_ctx* ctx, const pp_geom* gin, const pp_geom* gout, const double* affine_A, const double* affine_t,
                     const float* field, const float* image, int image_interp, double image_default, float* image_out,
                     const uint8_t* const* labels, int nlabels, uint8_t* const* labels_out);
+/* project_onto_arbitrary_plane (visualisation/utils.py:305-368: sitk.Resample through a rotation about the volume's centre,
+ * then sitk.{Sum,Mean,Median,StandardDeviation,Minimum,Maximum}Projection along an axis) for nviews transforms, one fp32
+ * image and nlabels uint8 label volumes, all on the grid g, in ONE launch.  views: HOST, nviews x 12 doubles, per view the
+ * row-major 3 x 3 A and then t of q = A p + t.  axis: 0 = x, 1 = y, 2 = z.  Outputs (DEVICE) are [nviews][rows][cols] with
+ * the two remaining axes ordered as sitk.GetArrayFromImage orders them: axis 0 -> [nz][ny], 1 -> [nz][nx], 2 -> [ny][nx].
+ * image (may be NULL: labels only) is sampled with image_interp (PP_INTERP_NEAREST or PP_INTERP_LINEAR), image_default
+ * outside, and reduced with `kind` into image_out (fp32); labels[l] (HOST array of nlabels device pointers, 0 ... 16) with
+ * label_interp[l] (HOST), 0 outside, reduced with max into labels_out[l] (uint8).  Every sample along a ray is, bit for bit,
+ * the voxel pp_resample_f32 / pp_resample_u8 write for that member, transform and output index with gout = gin = g (the
+ * default takes part in the reduction, as in the reference).  Reductions [ITK's accumulators as recalled, UNPINNED]: min, max;
+ * sum = the fp64 sum in index order, mean = sum / n, std = sqrt(sum((v - mean)^2) / (n - 1)) in fp64 in index order (NaN for
+ * n = 1), each rounded once to fp32; median = the element at index n / 2 of the sorted samples (std::nth_element: the upper
+ * median, no averaging).  NaN samples: min, max, sum, mean and std return NaN; the median sorts every NaN last (numpy's rule),
+ * so it is NaN only when more than (n - 1) / 2 samples are.  Nothing is atomic: reruns are bit-identical.  The median is a
+ * radix select that re-samples the ray (nine walks, no staging chunk, no scratch that grows with the volume).
+ * PP_INTERP_BSPLINE (image or label): PP_ERR_UNSUPPORTED (callers rotate member by member).  A bad axis or kind, an unknown
+ * interpolator, more than 16 labels or a negative count, nothing to project, nviews < 1, a NULL table or volume, an output
+ * that is an input or another output: PP_ERR_ARG.  More than 65535 output rows or views: PP_ERR_SIZE.  No error touches an
+ * output.  Scratch: 304 bytes per view.  Waits for the stream once, after queueing the copy of the views (host memory of the
+ * call); the kernel itself is only enqueued. */
+#define PP_PROJECT_MAX_LABELS 16
+enum { PP_PROJECT_SUM = 0, PP_PROJECT_MEAN = 1, PP_PROJECT_MEDIAN = 2, PP_PROJECT_STD = 3, PP_PROJECT_MIN = 4, PP_PROJECT_MAX = 5 };
+int pp_project_set(pp_ctx* ctx, const pp_geom* g, int axis, const double* views, int nviews, const float* image, int kind,
+                   int image_interp, double image_default, float* image_out, const uint8_t* const* labels, const int* label_interp,
+                   int nlabels, uint8_t* const* labels_out);
 /* itk::BSplineDecompositionImageFilter (spline order 3): samples -> B-spline coefficients, mirror boundaries; `out` may be
  * `in`.  pp_resample_f32 with interp = PP_INTERP_BSPLINE expects this coefficient volume as its input
  * (itk::BSplineInterpolateImageFunction: any sitk interpolator may reach registration/utils.py:176-190). */

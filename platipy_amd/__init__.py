@@ -54,3 +54,4 @@ from . import dicom  # noqa: E402,F401
 from . import generation  # noqa: E402,F401
 from . import utils  # noqa: E402,F401
 from . import projects  # noqa: E402,F401
+from . import visualisation  # noqa: E402,F401

@@ -52,6 +52,10 @@ class LinregStats(C.Structure):     # pp_linreg_stats
 ERR_ARG, ERR_SIZE = -1, -5
 ERR_UNSUPPORTED = -4
 RESAMPLE_SET_MAX_LABELS = 16    # PP_RESAMPLE_SET_MAX_LABELS
+PROJECT_MAX_LABELS = 16         # PP_PROJECT_MAX_LABELS
+PROJECT_SUM, PROJECT_MEAN, PROJECT_MEDIAN, PROJECT_STD, PROJECT_MIN, PROJECT_MAX = range(6)     # PP_PROJECT_*
+PROJECT_KINDS = {"sum": PROJECT_SUM, "mean": PROJECT_MEAN, "median": PROJECT_MEDIAN, "std": PROJECT_STD, "min": PROJECT_MIN,
+                 "max": PROJECT_MAX}
 ERR_NO_OVERLAP = -6
 ERR_DIRECTION = -7
 ERR_INVALID = -8        # PP_ERR_INVALID: a seed outside the buffer
@@ -172,6 +176,8 @@ _SIGNATURES = {
                                  _P, C.c_int, C.c_double, _P]),
     "pp_resample_set": (C.c_int, [_P, C.POINTER(Geom), C.POINTER(Geom), C.POINTER(C.c_double), C.POINTER(C.c_double), _P, _P, C.c_int,
                                   C.c_double, _P, C.POINTER(_P), C.c_int, C.POINTER(_P)]),
+    "pp_project_set": (C.c_int, [_P, C.POINTER(Geom), C.c_int, C.POINTER(C.c_double), C.c_int, _P, C.c_int, C.c_int, C.c_double, _P,
+                                 C.POINTER(_P), C.POINTER(C.c_int), C.c_int, C.POINTER(_P)]),
     "pp_resample_field_f32": (C.c_int, [_P, _P, C.POINTER(Geom), C.POINTER(Geom), _P]),
     "pp_bspline_prefilter_f32": (C.c_int, [_P, _P, C.POINTER(C.c_int), _P]),
     "pp_compose_field_f32": (C.c_int, [_P, _P, _P, C.POINTER(Geom)]),
@@ -473,6 +479,34 @@ class Context:
         if rc:
             msg = self.lib.pp_last_error(self.h)
             err = PlatipyAmdError(f"pp_resample_set failed ({rc}): {msg.decode(errors='replace') if msg else ''}")
+            err.code = rc
+            raise err
+
+    def project_set(self, geom, axis, views, image=None, image_out=None, kind=PROJECT_MAX, interp=INTERP_LINEAR, default_value=0.0,
+                    labels=(), labels_out=(), label_interp=INTERP_NEAREST):
+        """pp_project_set: the fp32 `image` (or None) and the uint8 `labels` (at most PROJECT_MAX_LABELS), all on `geom`,
+        through every transform of `views` ([nviews, 12]: row-major A, then t, of q = A p + t) and reduced along `axis`
+        (0 = x, 1 = y, 2 = z) in one launch: the image with `kind` (PROJECT_*) into image_out [nviews, rows, cols] fp32, every
+        label with max into labels_out[l] [nviews, rows, cols] uint8.  label_interp: one interpolator for all labels or one
+        per label.  Raises PlatipyAmdError with .code (ERR_UNSUPPORTED for sitkBSpline, ERR_ARG for a bad argument).
+        Waits for the stream while the views are uploaded; the kernel is only enqueued."""
+        if len(labels) != len(labels_out):
+            raise ValueError("project_set: one output per label")
+        n = len(labels)
+        v = np.ascontiguousarray(views, dtype=np.float64).reshape(-1)
+        if v.size % 12:
+            raise ValueError("project_set: `views` holds 12 doubles per view")
+        li = [int(label_interp)] * n if np.isscalar(label_interp) else [int(i) for i in label_interp]
+        if len(li) != n:
+            raise ValueError("project_set: one interpolator per label")
+        tin = (_P * max(n, 1))(*[ptr(x) for x in labels])
+        tout = (_P * max(n, 1))(*[ptr(x) for x in labels_out])
+        tli = (C.c_int * max(n, 1))(*li)
+        rc = self.lib.pp_project_set(self.h, C.byref(geom), int(axis), v.ctypes.data_as(C.POINTER(C.c_double)), v.size // 12, ptr(image),
+                                     int(kind), int(interp), float(default_value), ptr(image_out), tin, tli, n, tout)
+        if rc:
+            msg = self.lib.pp_last_error(self.h)
+            err = PlatipyAmdError(f"pp_project_set failed ({rc}): {msg.decode(errors='replace') if msg else ''}")
             err.code = rc
             raise err
 

@@ -965,3 +965,4 @@ int pp_compose_field_f32(pp_ctx* ctx, float* total, const float* iter, const pp_
 
 #include "pp_ventricle.h"   // pp_polar_sectors_u8, pp_resample_bits_u32 (uses the coordinate helpers above)
 #include "pp_field_inverse.h"   // pp_invert_field_f32, pp_inverse_consistency_f32, pp_jacobian_determinant_f32 (launch geometry above)
+#include "pp_project.h"   // pp_project_set: rotated projections of an image and its labels, all views in one launch (pp_map_point and the samplers above)
