@@ -98,6 +98,13 @@ void pp_reload_switches(void);
 int pp_create(int device, void* hip_stream, pp_ctx** out);
 void pp_destroy(pp_ctx* ctx);
 const char* pp_last_error(const pp_ctx* ctx);
+/* Every operation is asynchronous on the context's stream; the context's scratch, ticket counters and mailbox are shared by
+ * all of them.  pp_set_stream therefore WAITS (hipStreamSynchronize) for everything the context has queued on its current
+ * stream before it binds the new one, so work on the new stream never meets scratch that work on the old one still uses;
+ * setting the stream the context already has is free.  Results already queued keep their meaning: they are complete when
+ * the call returns.  The stream bound so far must therefore still be ALIVE when pp_set_stream is called: rebind first,
+ * destroy the old stream afterwards (a destroyed handle makes the wait fail with PP_ERR_HIP, or worse).  (No reference
+ * counterpart.) */
 int pp_set_stream(pp_ctx* ctx, void* hip_stream);
 int pp_sync(pp_ctx* ctx);
 size_t pp_workspace_bytes(const pp_ctx* ctx);

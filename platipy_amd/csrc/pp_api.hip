@@ -359,7 +359,11 @@ const char* pp_last_error(const pp_ctx* ctx) { return ctx ? ctx->err : "null ctx
 int pp_set_stream(pp_ctx* ctx, void* hip_stream) {
   if (!ctx) return PP_ERR_ARG;
   pp_device_guard dev_guard_(ctx);
-  ctx->stream = static_cast<hipStream_t>(hip_stream);
+  hipStream_t next = static_cast<hipStream_t>(hip_stream);
+  // the scratch, the ticket counters and the mailbox belong to whatever is still queued on the old stream: nothing issued to
+  // the new one may touch them before that has finished (the product binds a context to one stream for life: no cost there)
+  if (next != ctx->stream) PP_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  ctx->stream = next;
   return PP_OK;
 }
 

@@ -44,7 +44,7 @@ EXEMPT = {
     "pp_create": "allocates the context; every leg creates or reuses one",
     "pp_destroy": "frees the context; every fresh-context leg ends with it",
     "pp_last_error": "returns the context's host-side message",
-    "pp_set_stream": "stores a stream handle",
+    "pp_set_stream": "waits for the old stream, then stores the new handle (tests/test_stream_order.py holds it to that)",
     "pp_sync": "waits for the stream; every leg calls it before reading back",
     "pp_workspace_bytes": "returns a host-side size; the garbage-A leg reads it",
     "pp_profile_enable": "host-side switch of the event brackets",
