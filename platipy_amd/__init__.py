@@ -55,3 +55,4 @@ from . import generation  # noqa: E402,F401
 from . import utils  # noqa: E402,F401
 from . import projects  # noqa: E402,F401
 from . import visualisation  # noqa: E402,F401
+from . import radiomics  # noqa: E402,F401

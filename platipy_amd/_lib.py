@@ -125,6 +125,7 @@ CONTOUR_DTYPE = np.dtype([("first", "<i4"), ("count", "<i4"), ("structure", "<i4
 CONTOUR_CHUNK, CONTOUR_MAX_INDEX = 256, 1 << 24
 
 DOSE_MAX_LABELS, DOSE_MAX_BINS, ORDER_STATS_MAX_RANKS = 64, 1 << 20, 8
+TEXTURE_MAX_NG, TEXTURE_LDS_WORDS, DISCRETISE_MAX_LEVELS = 1024, 8192, 65535     # TX_MAX_NG, TX_LDS_WORDS, RD_MAX_LEVELS of csrc/pp_radiomics.h
 # pp_dose_stats as a numpy record
 DOSE_STATS_DTYPE = np.dtype([("count", "<i8"), ("mask_sum", "<i8"), ("dose_sum", "<f8"), ("dose_min", "<f4"), ("dose_max", "<f4")])
 
@@ -207,6 +208,12 @@ _SIGNATURES = {
     "pp_masked_order_stats_f32": (C.c_int, [_P, _P, _P, C.c_size_t, C.POINTER(C.c_int64), C.c_int, C.POINTER(C.c_float)]),
     "pp_masked_count_ge_f32": (C.c_int, [_P, _P, C.POINTER(_P), C.c_int, C.c_size_t, C.POINTER(C.c_float), C.c_int,
                                          C.POINTER(C.c_int64)]),
+    "pp_masked_moments_f32": (C.c_int, [_P, _P, _P, C.c_size_t, C.c_double, C.c_double, C.c_double, C.POINTER(C.c_int64),
+                                        C.POINTER(C.c_double)]),
+    "pp_radiomics_discretise_f32": (C.c_int, [_P, _P, _P, C.c_size_t, C.POINTER(C.c_double), C.c_int, _P]),
+    "pp_texture_neighbourhood_u16": (C.c_int, [_P, _P, C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_int64),
+                                               C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "pp_texture_runs_u16": (C.c_int, [_P, _P, C.POINTER(C.c_int), C.c_int, C.c_int, C.POINTER(C.c_int64)]),
     "pp_label_contour_u8": (C.c_int, [_P, _P, C.POINTER(C.c_int), _P]),
     "pp_distance_map_f32": (C.c_int, [_P, _P, C.POINTER(Geom), C.c_int, C.c_int, _P]),
     "pp_overlap_counts_u8": (C.c_int, [_P, _P, _P, C.c_size_t, C.POINTER(C.c_int64)]),
@@ -772,6 +779,58 @@ class Context:
                                              int(t.size), counts.ctypes.data_as(C.POINTER(C.c_int64)))
         self._chk_value(rc, "pp_masked_count_ge_f32")
         return counts
+
+    # -- radiomics ----------------------------------------------------------------
+    def masked_moments(self, image, mask, n, lo=-np.inf, hi=np.inf, centre=0.0):
+        """pp_masked_moments_f32 -> (count, float64 [6]): over the voxels of the uint8 mask with lo <= v <= hi, the sums of
+        v - c, |v - c|, (v - c)^2, (v - c)^3, (v - c)^4 and v^2 in fp64, bit-identical from call to call (synchronises)."""
+        count = C.c_int64(0)
+        sums = np.zeros(6, dtype=np.float64)
+        rc = self.lib.pp_masked_moments_f32(self.h, ptr(image), ptr(mask), int(n), float(lo), float(hi), float(centre), C.byref(count),
+                                            sums.ctypes.data_as(C.POINTER(C.c_double)))
+        self._chk_value(rc, "pp_masked_moments_f32")
+        return int(count.value), sums
+
+    def radiomics_discretise(self, image, mask, n, edges, levels):
+        """pp_radiomics_discretise_f32: levels (uint16 device memory, n voxels; torch has no uint16 arithmetic, an int16 tensor
+        serves) = np.digitize(image, edges) inside the uint8 mask, 0 outside.  ValueError for a NaN, an infinity or a value
+        outside the edges inside the mask, and for more than 65535 levels."""
+        e = np.ascontiguousarray(edges, dtype=np.float64).reshape(-1)
+        have = _nbytes(levels)
+        if have is not None and have != 2 * int(n):
+            raise ValueError(f"pp_radiomics_discretise_f32: `levels` holds {have} bytes for {n} voxels")
+        rc = self.lib.pp_radiomics_discretise_f32(self.h, ptr(image), ptr(mask), int(n), e.ctypes.data_as(C.POINTER(C.c_double)), int(e.size),
+                                                  ptr(levels))
+        self._chk_value(rc, "pp_radiomics_discretise_f32")
+
+    def texture_neighbourhood(self, levels, size, ng, glcm=True, gldm=True, ngtdm=True):
+        """pp_texture_neighbourhood_u16 -> dict of int64 arrays: "glcm" [13, ng, ng] (forward counts; the symmetric matrix is
+        g + g.transpose(0, 2, 1)), "gldm" [ng, 27], "ngtdm_n" and "ngtdm_s" [ng, 27], those asked for (synchronises).
+        ValueError for ng outside 1 ... TEXTURE_MAX_NG or a level above ng."""
+        _check_volume("pp_texture_neighbourhood_u16", size, levels=(levels, 2))
+        ng = int(ng)
+        ok = 1 <= ng <= TEXTURE_MAX_NG          # (a refused call allocates nothing)
+        out = {}
+        if glcm:
+            out["glcm"] = np.zeros((13, ng, ng) if ok else (0,), dtype=np.int64)
+        if gldm:
+            out["gldm"] = np.zeros((ng, 27) if ok else (0,), dtype=np.int64)
+        if ngtdm:
+            out["ngtdm_n"] = np.zeros((ng, 27) if ok else (0,), dtype=np.int64)
+            out["ngtdm_s"] = np.zeros((ng, 27) if ok else (0,), dtype=np.int64)
+        p = lambda k: out[k].ctypes.data_as(C.POINTER(C.c_int64)) if k in out else None  # noqa: E731
+        rc = self.lib.pp_texture_neighbourhood_u16(self.h, ptr(levels), _i3(size), ng, p("glcm"), p("gldm"), p("ngtdm_n"), p("ngtdm_s"))
+        self._chk_value(rc, "pp_texture_neighbourhood_u16")
+        return out
+
+    def texture_runs(self, levels, size, ng):
+        """pp_texture_runs_u16 -> int64 [13, ng, max(size)]: the run-length table of every direction (synchronises)."""
+        _check_volume("pp_texture_runs_u16", size, levels=(levels, 2))
+        ng, nr = int(ng), max(int(s) for s in size)
+        out = np.zeros((13, ng, nr) if 1 <= ng <= TEXTURE_MAX_NG else (0,), dtype=np.int64)
+        rc = self.lib.pp_texture_runs_u16(self.h, ptr(levels), _i3(size), ng, nr, out.ctypes.data_as(C.POINTER(C.c_int64)))
+        self._chk_value(rc, "pp_texture_runs_u16")
+        return out
 
     # -- vessel splining ------------------------------------------------------------
     def slice_moments(self, masks, size, axis, out):

@@ -1544,3 +1544,7 @@ int pp_linear_set_sample_jitter(pp_ctx* ctx, const float* jitter, size_t nsample
 
 // masks to RTSTRUCT contours (dicom/io/nifti_to_rtstruct.py): pp_contour_trace_u8
 #include "pp_contour_trace.h"
+
+// radiomics: first-order moments, discretisation and the texture tables (services/radiomics/service.py): pp_masked_moments_f32,
+// pp_radiomics_discretise_f32, pp_texture_neighbourhood_u16, pp_texture_runs_u16
+#include "pp_radiomics.h"
