@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define PP_ABI_VERSION 5
+#define PP_ABI_VERSION 6
 
 typedef enum {
   PP_OK = 0,
@@ -442,6 +442,44 @@ int pp_texture_neighbourhood_u16(pp_ctx* ctx, const uint16_t* levels, const int 
  * another level; its thread walks the run.  Integer atomics only (LDS counters for runs of up to 8 voxels while ng <= 78): a
  * rerun gives the same bits.  Limits and errors as pp_texture_neighbourhood_u16.  Synchronises. */
 int pp_texture_runs_u16(pp_ctx* ctx, const uint16_t* levels, const int size[3], int ng, int nr, int64_t* glrlm);
+
+/* ---- SIFT landmarks for deformable-registration QA ---------------------------------- */
+/* The hot paths behind the reference's DIR QA service (services/dirqa/service.py:60-140 runs `plastimatch sift` on two
+ * cropped, windowed images and keeps the matches inside a contour).  Neither plastimatch nor ITK's SIFT filter is available
+ * where this was written: parity with them is UNPINNED and the semantics are this build's own rules S1 ... S7 (stated in
+ * csrc/pp_sift.h and DESIGN 4.17, restated in numpy by tests/sift_restatement.py).  All four promise identical bits on a rerun.
+ *
+ * gauss: DEVICE, one octave's nlevels = intervals + 3 (4 ... 8) Gaussian volumes of size = {x, y, z}, one after another.
+ * D_l = G_{l+1} - G_l (one fp32 subtraction, never written).  A voxel of a level 1 <= l <= nlevels - 3, at least one voxel
+ * from every face, is a candidate when D_l is strictly greater, or strictly smaller, than its 80 neighbours (S3); it is
+ * refined and tested in fp64 (S4: one clamped Newton step, |response| / range >= contrast_threshold, definite Hessian,
+ * trace^3 / det < curvature_threshold).  candidates_only != 0 skips S4 (offset 0, response = D; range and thresholds unused).
+ * Outputs are HOST: *count = the kept keypoints, and the first min(count, capacity) of them in ascending (level, z, y, x)
+ * (S5): index[k] = {x, y, z, level}, values[k] = {offset x, y, z, response}; rows beyond are untouched.  An axis shorter
+ * than 3: count 0, nothing launched.  A range that is not positive and finite, a NaN threshold, nlevels outside 4 ... 8:
+ * PP_ERR_ARG; 2^31 voxels or more: PP_ERR_SIZE.  Synchronises. */
+int pp_dog_extrema_f32(pp_ctx* ctx, const float* gauss, const int size[3], int nlevels, double range, double contrast_threshold,
+                       double curvature_threshold, int candidates_only, int capacity, int32_t* index, double* values, int64_t* count);
+/* descriptors (DEVICE fp32 [n][768], every entry written) of n keypoints (HOST int32 [n][4] = {x, y, z, level}, level = the
+ * Gaussian volume of `gauss` to describe on): the gradient-orientation histogram of S6 -- 16^3 voxels about the keypoint
+ * (edge replicate), 4^3 cells x 12 icosahedron-vertex bins, Gaussian window, fp64 sums in a fixed order, L2-normalise, clip at
+ * 0.2, normalise again.  Not rotation invariant.  spacing = {x, y, z} mm.  A keypoint outside the stack: PP_ERR_ARG before
+ * anything is launched.  Synchronises (the keypoints are staged from the caller's array). */
+int pp_sift_describe_f32(pp_ctx* ctx, const float* gauss, const int size[3], int nlevels, const double spacing[3],
+                         const int32_t* keypoints, int n, float* descriptors);
+/* For every row i of a (DEVICE fp32 [na][length]): best_index[i] (DEVICE int32) = the row of b (DEVICE fp32 [nb][length]) at
+ * the smallest squared L2 distance (fp32, components in ascending order, one fused multiply-add each), the lowest index on a
+ * tie; best[i], second[i] (DEVICE fp32) = the smallest and second-smallest distance (S7).  With points_a / points_b (DEVICE
+ * fp64 [n][3], both or neither) only rows of b within `radius` of row i's point take part.  No row takes part: -1, +inf,
+ * +inf; one: second = +inf.  Any length >= 1.  The rows of b are split over workgroups and the partial results folded in a fixed
+ * order (context scratch: 12 bytes per row of a and segment); the result does not depend on the split.  No synchronisation. */
+int pp_descriptor_match_f32(pp_ctx* ctx, const float* a, int na, const float* b, int nb, int length, const double* points_a,
+                            const double* points_b, double radius, int32_t* best_index, float* best, float* second);
+/* out[k] (HOST fp64 [n][3]) = points[k] + D(points[k]) for physical points (HOST fp64 [n][3]) and a planar fp32 displacement
+ * field (DEVICE [3][nz][ny][nx], mm) with geometry g: the continuous index of pp_resample_f32's own map, fp64 trilinear
+ * interpolation with ITK's clamped upper corner; a point outside [-0.5, n - 0.5) on any axis moves by zero, as
+ * itk::DisplacementFieldTransform leaves it [ITK-upstream, unverified here].  Synchronises. */
+int pp_transform_points_f64(pp_ctx* ctx, const float* field, const pp_geom* g, const double* points, int n, double* out);
 
 /* ---- iterative atlas removal ------------------------------------------------------- */
 /* sitk.LabelContour(mask) with face connectivity (label/projection.py:85): object voxels that have a face

@@ -18,7 +18,7 @@ INTERP_NEAREST = 1
 INTERP_LINEAR = 2
 INTERP_BSPLINE = 3
 DEMONS_AUTO, DEMONS_STAGED, DEMONS_FUSED = 0, 1, 2
-ABI_VERSION = 5
+ABI_VERSION = 6
 HISTORY_CAPACITY = 4096     # PP_DEMONS_HISTORY_CAPACITY: iterations of one Execute whose metric / RMS change the device ring keeps
 
 
@@ -214,6 +214,11 @@ _SIGNATURES = {
     "pp_texture_neighbourhood_u16": (C.c_int, [_P, _P, C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_int64),
                                                C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "pp_texture_runs_u16": (C.c_int, [_P, _P, C.POINTER(C.c_int), C.c_int, C.c_int, C.POINTER(C.c_int64)]),
+    "pp_dog_extrema_f32": (C.c_int, [_P, _P, C.POINTER(C.c_int), C.c_int, C.c_double, C.c_double, C.c_double, C.c_int, C.c_int,
+                                     C.POINTER(C.c_int32), C.POINTER(C.c_double), C.POINTER(C.c_int64)]),
+    "pp_sift_describe_f32": (C.c_int, [_P, _P, C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_int32), C.c_int, _P]),
+    "pp_descriptor_match_f32": (C.c_int, [_P, _P, C.c_int, _P, C.c_int, C.c_int, _P, _P, C.c_double, _P, _P, _P]),
+    "pp_transform_points_f64": (C.c_int, [_P, _P, C.POINTER(Geom), C.POINTER(C.c_double), C.c_int, C.POINTER(C.c_double)]),
     "pp_label_contour_u8": (C.c_int, [_P, _P, C.POINTER(C.c_int), _P]),
     "pp_distance_map_f32": (C.c_int, [_P, _P, C.POINTER(Geom), C.c_int, C.c_int, _P]),
     "pp_overlap_counts_u8": (C.c_int, [_P, _P, _P, C.c_size_t, C.POINTER(C.c_int64)]),
@@ -830,6 +835,58 @@ class Context:
         out = np.zeros((13, ng, nr) if 1 <= ng <= TEXTURE_MAX_NG else (0,), dtype=np.int64)
         rc = self.lib.pp_texture_runs_u16(self.h, ptr(levels), _i3(size), ng, nr, out.ctypes.data_as(C.POINTER(C.c_int64)))
         self._chk_value(rc, "pp_texture_runs_u16")
+        return out
+
+    # -- SIFT landmarks (DIR QA) --------------------------------------------------------
+    def dog_extrema(self, gauss, size, nlevels, value_range, contrast_threshold, curvature_threshold, capacity, candidates_only=False):
+        """pp_dog_extrema_f32 over one octave's stack of `nlevels` Gaussian volumes -> (count, int32 [rows, 4] = x, y, z, level,
+        float64 [rows, 4] = offset x, y, z, response) with rows = min(count, capacity), in ascending (level, z, y, x)
+        (synchronises)."""
+        _check_volume("pp_dog_extrema_f32", (int(size[0]), int(size[1]), int(size[2]) * int(nlevels)), gauss=(gauss, 4))
+        capacity = max(int(capacity), 0)
+        index, values, count = np.zeros((capacity, 4), np.int32), np.zeros((capacity, 4), np.float64), C.c_int64(0)
+        rc = self.lib.pp_dog_extrema_f32(self.h, ptr(gauss), _i3(size), int(nlevels), float(value_range), float(contrast_threshold),
+                                         float(curvature_threshold), int(bool(candidates_only)), capacity,
+                                         index.ctypes.data_as(C.POINTER(C.c_int32)), values.ctypes.data_as(C.POINTER(C.c_double)),
+                                         C.byref(count))
+        self._chk_value(rc, "pp_dog_extrema_f32")
+        rows = min(int(count.value), capacity)
+        return int(count.value), index[:rows], values[:rows]
+
+    def sift_describe(self, gauss, size, nlevels, spacing, keypoints, descriptors):
+        """pp_sift_describe_f32: descriptors (fp32 device memory [n, 768]) of the keypoints (int32 [n, 4] = x, y, z, level, a
+        host array) on the stack `gauss` (synchronises)."""
+        _check_volume("pp_sift_describe_f32", (int(size[0]), int(size[1]), int(size[2]) * int(nlevels)), gauss=(gauss, 4))
+        kp = np.ascontiguousarray(keypoints, dtype=np.int32).reshape(-1, 4)
+        have = _nbytes(descriptors)
+        if have is not None and have != kp.shape[0] * 768 * 4:
+            raise ValueError(f"pp_sift_describe_f32: `descriptors` holds {have} bytes for {kp.shape[0]} keypoints")
+        rc = self.lib.pp_sift_describe_f32(self.h, ptr(gauss), _i3(size), int(nlevels), _d3(spacing), kp.ctypes.data_as(C.POINTER(C.c_int32)),
+                                           int(kp.shape[0]), ptr(descriptors))
+        self._chk_value(rc, "pp_sift_describe_f32")
+
+    def descriptor_match(self, a, na, b, nb, length, best_index, best, second, points_a=None, points_b=None, radius=0.0):
+        """pp_descriptor_match_f32: for every row of a [na, length] the nearest row of b [nb, length] (int32 device memory
+        `best_index`) and the two smallest squared distances (fp32 device memory `best`, `second`); with fp64 device point lists
+        only rows of b within `radius` take part.  Nothing is read back."""
+        for what, buf, want in (("a", a, na * length * 4), ("b", b, nb * length * 4), ("best_index", best_index, na * 4), ("best", best, na * 4),
+                                ("second", second, na * 4), ("points_a", points_a, na * 24), ("points_b", points_b, nb * 24)):
+            have = None if buf is None else _nbytes(buf)
+            if have is not None and have != int(want):
+                raise ValueError(f"pp_descriptor_match_f32: `{what}` holds {have} bytes, {int(want)} expected")
+        rc = self.lib.pp_descriptor_match_f32(self.h, ptr(a), int(na), ptr(b), int(nb), int(length), ptr(points_a), ptr(points_b), float(radius),
+                                              ptr(best_index), ptr(best), ptr(second))
+        self._chk_value(rc, "pp_descriptor_match_f32")
+
+    def transform_points(self, field, geom, points):
+        """pp_transform_points_f64 -> float64 [n, 3]: p + D(p) for physical points through the planar fp32 field [3, Z, Y, X] on
+        `geom`; zero displacement outside the field (synchronises)."""
+        _check_volume("pp_transform_points_f64", (int(geom.size[0]), int(geom.size[1]), int(geom.size[2]) * 3), field=(field, 4))
+        p = np.ascontiguousarray(points, dtype=np.float64).reshape(-1, 3)
+        out = np.zeros_like(p)
+        rc = self.lib.pp_transform_points_f64(self.h, ptr(field), C.byref(geom), p.ctypes.data_as(C.POINTER(C.c_double)), int(p.shape[0]),
+                                              out.ctypes.data_as(C.POINTER(C.c_double)))
+        self._chk_value(rc, "pp_transform_points_f64")
         return out
 
     # -- vessel splining ------------------------------------------------------------

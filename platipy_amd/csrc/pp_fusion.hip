@@ -1548,3 +1548,7 @@ int pp_linear_set_sample_jitter(pp_ctx* ctx, const float* jitter, size_t nsample
 // radiomics: first-order moments, discretisation and the texture tables (services/radiomics/service.py): pp_masked_moments_f32,
 // pp_radiomics_discretise_f32, pp_texture_neighbourhood_u16, pp_texture_runs_u16
 #include "pp_radiomics.h"
+
+// SIFT landmarks for DIR QA (services/dirqa/service.py): pp_dog_extrema_f32, pp_sift_describe_f32, pp_descriptor_match_f32,
+// pp_transform_points_f64
+#include "pp_sift.h"

@@ -19,3 +19,13 @@ from .field import (  # noqa: F401
     invert_displacement_field,
 )
 from ..label.region import connected_threshold  # noqa: E402,F401  (sitk.ConnectedThreshold: a region-growing segmentation filter)
+from .qa import (  # noqa: E402,F401
+    DIRQA_SETTINGS_DEFAULTS,
+    Keypoints,
+    PointTable,
+    dir_qa,
+    match_keypoints,
+    sift_keypoints,
+    target_registration_error,
+    transform_points,
+)
