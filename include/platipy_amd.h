@@ -239,7 +239,13 @@ int pp_compose_field_f32(pp_ctx* ctx, float* total, const float* iter, const pp_
 int pp_demons_force_f32(pp_ctx* ctx, const float* fixed, const float* warped, const pp_geom* g,
                         const pp_demons_params* p, float* update, pp_demons_stats* stats);
 /* registration_algorithm.Execute(f_image, m_image) (deformable.py:149): the whole inner
- * loop on device, field starting from zero.  stats may be NULL (then fully asynchronous). */
+ * loop on device, field starting from zero.  stats may be NULL (then fully asynchronous).
+ * Alignment: fixed and moving need no more than their natural 4 bytes under either variant (a view that starts at any
+ * element of a larger buffer gives the bits of an aligned one).  PP_DEMONS_FUSED needs `field` on a 16-byte boundary (its
+ * kernels store the field as 8- and 16-byte vectors): otherwise PP_ERR_UNSUPPORTED, "fused demons needs field on a
+ * 16-byte boundary", before anything is launched; the same status with its own message says that a smoother is off or a
+ * kernel radius is above 5.  PP_DEMONS_AUTO takes the staged variant in each of these cases, which accepts any 4-byte
+ * aligned field; PP_DEMONS_STAGED never looks at the alignment. */
 int pp_demons_execute_f32(pp_ctx* ctx, const float* fixed, const float* moving, const pp_geom* g,
                           const pp_demons_params* p, float* field, pp_demons_stats* stats);
 /* What an sitkIterationEvent observer of the filter reads after every iteration -- registration_method.AddCommand(
@@ -515,7 +521,10 @@ int pp_abs_range_f32(pp_ctx* ctx, const float* in, size_t n, float* device_range
  * out (DEVICE, 8-byte aligned): count, fp64 sum and sum of squares, min, max, the count of values <= tau and, when
  * device_range (DEVICE, 2 floats {lo, hi}, e.g. from pp_abs_range_f32) is not NULL, ITK's 128-bin histogram of the values
  * over [lo, hi]: bin = min(int((v - lo) / (hi - lo) * 128), 127) in fp64.  Sums run in a fixed order and the bins are
- * integers: a rerun gives the same bits.  No read-back, no synchronisation. */
+ * integers: a rerun ON THE SAME BUFFERS gives the same bits.  The order follows the alignment of `select`: on a 16-byte
+ * boundary a thread sums 16 consecutive voxels (and the grid is sized for that), elsewhere one voxel per step, so
+ * `sum` and `sum_sq` of a select that starts elsewhere may differ from an aligned one's in the last bits (fp64 rounding of
+ * the same samples); every other member does not depend on it.  No read-back, no synchronisation. */
 enum { PP_SURFACE_CONTOUR_ABS = 0, PP_SURFACE_LABEL_POS = 1, PP_SURFACE_NONZERO = 2 };
 #define PP_SURFACE_BINS 128
 typedef struct pp_surface_stats {
@@ -529,7 +538,8 @@ typedef struct pp_surface_stats {
 int pp_surface_stats_f32(pp_ctx* ctx, const uint8_t* select, const float* dist, const pp_geom* g, int mode, double tau,
                          const float* device_range, pp_surface_stats* out);
 /* Per z slice, the number of voxels with a != 0 and not_b == 0 (not_b may be NULL: the count of a): sitk.MaskNegated +
- * sum per slice, and the "both slices empty" test (label/comparison.py:367-385).  per_slice: DEVICE, size[2] x int64.
+ * sum per slice, and the "both slices empty" test (label/comparison.py:367-385).  per_slice: DEVICE, size[2] x int64, 8-byte
+ * aligned (PP_ERR_ARG otherwise); a and not_b at any address, the counts do not depend on it.
  * No read-back, no synchronisation. */
 int pp_slice_masked_count_u8(pp_ctx* ctx, const uint8_t* a, const uint8_t* not_b, const int size[3], int64_t* per_slice);
 

@@ -1184,13 +1184,21 @@ int pp_demons_execute_f32(pp_ctx* ctx, const float* fixed, const float* moving, 
     if (td[a].r > rmax) rmax = td[a].r;
   }
   // the fused kernels address one z-plane with 32-bit byte offsets and store 8/16-B vectors
-  const bool plane_ok = (size_t)d.nx * d.ny * sizeof(float) < ((size_t)1 << 32) && (reinterpret_cast<uintptr_t>(field) % 16 == 0);
-  const bool fusable = p->smooth_update && p->smooth_displacement && rmax <= PP_FUSED_MAX_R && plane_ok;
+  const bool plane_ok = (size_t)d.nx * d.ny * sizeof(float) < ((size_t)1 << 32);
+  const bool field_ok = reinterpret_cast<uintptr_t>(field) % 16 == 0;
+  const bool smooth_ok = p->smooth_update && p->smooth_displacement && rmax <= PP_FUSED_MAX_R;
+  const bool fusable = smooth_ok && plane_ok && field_ok;
   int variant = p->variant;
   if (variant == PP_DEMONS_AUTO) variant = fusable ? PP_DEMONS_FUSED : PP_DEMONS_STAGED;
-  if (variant == PP_DEMONS_FUSED && !fusable)
+  if (variant == PP_DEMONS_FUSED && !smooth_ok)
     return pp_fail(ctx, PP_ERR_UNSUPPORTED,
                    "fused demons needs both smoothers on and kernel radii <= %d (got %d)", PP_FUSED_MAX_R, rmax);
+  if (variant == PP_DEMONS_FUSED && !plane_ok)
+    return pp_fail(ctx, PP_ERR_UNSUPPORTED, "fused demons needs a z-plane below 4 GiB (got %d x %d voxels)", d.nx, d.ny);
+  if (variant == PP_DEMONS_FUSED && !field_ok)
+    return pp_fail(ctx, PP_ERR_UNSUPPORTED,
+                   "fused demons needs field on a 16-byte boundary (got an address at %d mod 16); PP_DEMONS_AUTO takes the staged variant",
+                   (int)(reinterpret_cast<uintptr_t>(field) % 16));
   PP_REQUIRE(ctx, variant == PP_DEMONS_FUSED || variant == PP_DEMONS_STAGED, "demons: unknown variant");
 
   pp_esm_consts K;

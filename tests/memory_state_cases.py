@@ -39,10 +39,12 @@ class Leg:
     def _pattern(self, dtype):
         return self.fpat if np.dtype(dtype).kind == "f" else self.ipat
 
-    def dev(self, a):
+    def dev(self, a, align=None):
+        """`align`: the alignment in bytes that include/platipy_amd.h requires of this buffer.  Whole allocations have it; the
+        offset views of tests/buffer_views.py keep it."""
         return self.be.dev(a if a.flags.writeable else a.copy())       # (the shared, read-only inputs of other test modules)
 
-    def p(self, a):
+    def p(self, a, align=None):
         """The address of `a` on the backend, for a raw call; the buffer lives as long as the leg."""
         self._keep.append(self.dev(a))
         return _lib.ptr(self._keep[-1])
@@ -51,7 +53,7 @@ class Leg:
         self.ctx.sync()
         return np.array(h.cpu().numpy() if hasattr(h, "cpu") else h)
 
-    def empty(self, shape, dtype=np.float32):
+    def empty(self, shape, dtype=np.float32, align=None):
         return self.be.garbage(shape, dtype, self._pattern(dtype))
 
     def hempty(self, shape, dtype=np.float64):
@@ -482,7 +484,8 @@ def _demons_execute(gname, variant, mode):
 
     def run(leg):
         fix, mov = _execute_inputs(gname, mode)[:2]
-        fld, st = leg.empty((3,) + shape), leg.hstruct(_lib.DemonsStats)
+        # (PP_DEMONS_FUSED wants the field on 16 bytes, include/platipy_amd.h; the staged variant takes any)
+        fld, st = leg.empty((3,) + shape, align=16 if variant == _lib.DEMONS_FUSED else None), leg.hstruct(_lib.DemonsStats)
         assert call(leg, leg.dev(fix), leg.dev(mov), fld, st) == 0
         out = {"field": leg.host(fld), **fields(st)}
         metric, rms = leg.hempty(16), leg.hempty(16)         # pp_demons_history: what an iteration observer reads
@@ -1091,7 +1094,7 @@ def _compare():
             out = {}
             for mode in (0, 1, 2):
                 for ranged in (True, False):
-                    rec = leg.empty((_lib.SURFACE_STATS_DTYPE.itemsize,), np.uint8)
+                    rec = leg.empty((_lib.SURFACE_STATS_DTYPE.itemsize,), np.uint8, align=8)
                     leg.ctx.surface_stats(dsel, ddist, geom, mode, rec, tau=tau, device_range=drange if ranged else None)
                     out[f"mode{mode}-range{int(ranged)}"] = leg.host(rec)
             return out
@@ -1121,7 +1124,7 @@ def _compare():
         def run_smc(leg, shape=shape, size=size, a=a, b=b):
             out = {}
             for name, nb in (("masked", b), ("plain", None)):
-                o = leg.empty((shape[0],), np.int64)
+                o = leg.empty((shape[0],), np.int64, align=8)
                 leg.ctx.slice_masked_count(leg.dev(a), None if nb is None else leg.dev(nb), size, o)
                 out[name] = leg.host(o)
             return out
@@ -1309,7 +1312,7 @@ def _linear_metrics(key, setter=None):
                 self.keep = leg.dev(jit)
                 leg.ctx.set_sample_jitter(self.keep)
             elif setter == "gimg":
-                self.keep = (leg.dev(GI), leg.dev(np.ascontiguousarray(np.concatenate([np.moveaxis(GI, 0, -1), M[..., None]], axis=-1))))
+                self.keep = (leg.dev(GI), leg.dev(np.ascontiguousarray(np.concatenate([np.moveaxis(GI, 0, -1), M[..., None]], axis=-1)), align=16))
                 leg.ctx.set_moving_gradient(self.keep[0], LM.size_of(c["mshape"]), packed=self.keep[1])
             return LM.call_args(leg, key)
 
@@ -1533,8 +1536,8 @@ def _bspline_metric(k):
     def run(leg):
         d, jit, fm, mm = parts()
         ctx = leg.ctx
-        dev = lambda a: None if a is None else leg.dev(a)        # noqa: E731
-        keep = [dev(d["fixed"]), dev(d["moving"]), dev(coef), dev(fm), dev(mm), dev(jit), dev(d["grad"]), dev(d["packed"])]
+        dev = lambda a, **kw: None if a is None else leg.dev(a, **kw)        # noqa: E731
+        keep = [dev(d["fixed"]), dev(d["moving"]), dev(coef), dev(fm), dev(mm), dev(jit), dev(d["grad"]), dev(d["packed"], align=16)]
         geom, mgeom, lgeom = _lib.make_geom(B.SIZE, B.SPACING, B.ORIGIN, B.EYE), _lib.make_geom(*B.MOVING[:3], B.MOVING[3].ravel()), B._lat_geom(lat)
         value, st, grad = leg.hempty(1), leg.hempty(4), leg.hempty(coef.size)
         try:
@@ -1579,7 +1582,9 @@ def _bspline_mi(name):
     def run(leg):
         c = BM._case(name)
         nb = c["nbins"]
-        with BM._Installed(leg, c) as k:
+        inst = BM._Installed(leg, c)
+        inst.keep[7] = leg.dev(BM._inputs()["packed"], align=16)       # (the header wants the packed image on 16 bytes)
+        with inst as k:
             fixed, geom, moving, mgeom, vgeom, stride, coefd, lgeom, bins = k.args
             head = (leg.ctx.h, _lib.ptr(fixed), C.byref(geom), _lib.ptr(moving), C.byref(mgeom), C.byref(vgeom), int(stride), _lib.ptr(k.kw["fixed_mask"]),
                     _lib.ptr(k.kw["moving_mask"]), _lib.ptr(coefd), C.byref(lgeom), float(k.kw["jitter_bound"]), C.byref(bins))

@@ -215,14 +215,19 @@ def _garbage_allocators(monkeypatch):
     monkeypatch.setattr(torch.Tensor, "new_empty", lambda self, *a, **k: filled(new_empty(self, *a, **k)))
 
 
-def _path_demons(pa):
+# Every builder takes `images`: an object whose image_from_array(array, spacing, origin) makes the INPUT images (None: the
+# package's own, a plain upload).  tests/test_buffer_views.py passes one that puts every input into an offset view.
+
+
+def _path_demons(pa, images=None):
     from tests.helpers import phantom, random_dvf
     from oracle import oracle as O
     shape, spacing = (12, 20, 72), (1.0, 1.0, 1.0)
     fix = phantom(shape, seed=40)
     dv = random_dvf(shape, spacing, seed=41, max_mm=2.5)
     mov = O.warp_image(O.Vol(fix, spacing, (0.0, 0.0, 0.0)), dv.astype(np.float64), edge_value=-1000.0).arr.astype(np.float32)
-    f, m = pa.image_from_array(fix, spacing), pa.image_from_array(mov, spacing)
+    mk = (images or pa).image_from_array
+    f, m = mk(fix, spacing), mk(mov, spacing)
 
     def run():
         img, _, dvf = pa.registration.fast_symmetric_forces_demons_registration(f, m, resolution_staging=[2, 1], iteration_staging=[4, 3])
@@ -230,11 +235,12 @@ def _path_demons(pa):
     return run
 
 
-def _path_linear(pa):
+def _path_linear(pa, images=None):
     from tests.test_linear import _rigid_pair
     shape, spacing, origin = (16, 20, 24), (1.5, 1.5, 2.5), (-30.0, -20.0, 10.0)
     fix, mov, _ = _rigid_pair(pa, shape, spacing, origin, angle=0.05, shift=(1.5, -1.0, 1.0))
-    f, m = pa.image_from_array(fix, spacing, origin), pa.image_from_array(mov, spacing, origin)
+    mk = (images or pa).image_from_array
+    f, m = mk(fix, spacing, origin), mk(mov, spacing, origin)
 
     def run():
         img, tfm = pa.registration.linear_registration(f, m, reg_method="affine", optimiser="gradient_descent_line_search", shrink_factors=[2, 1],
@@ -243,13 +249,14 @@ def _path_linear(pa):
     return run
 
 
-def _path_combine_labels(pa):
+def _path_combine_labels(pa, images=None):
     from tests.helpers import phantom, smooth_noise
     from tests.test_kernels import GRIDS
     shape, spacing, origin = GRIDS[0]
-    tgt = pa.image_from_array(phantom(shape, seed=70), spacing, origin)
-    atl = [pa.image_from_array(phantom(shape, seed=70, noise=0) + 30 * smooth_noise(shape, 71 + i).astype(np.float32), spacing, origin) for i in range(3)]
-    labels = [pa.image_from_array((smooth_noise(shape, 80 + i, cells=4) > 0.1).astype(np.uint8), spacing, origin) for i in range(3)]
+    mk = (images or pa).image_from_array
+    tgt = mk(phantom(shape, seed=70), spacing, origin)
+    atl = [mk(phantom(shape, seed=70, noise=0) + 30 * smooth_noise(shape, 71 + i).astype(np.float32), spacing, origin) for i in range(3)]
+    labels = [mk((smooth_noise(shape, 80 + i, cells=4) > 0.1).astype(np.uint8), spacing, origin) for i in range(3)]
 
     def run():
         aset = {str(i): {"DIR": {"Weight Map": pa.label.compute_weight_map(tgt, atl[i], vote_type="local"), "S": labels[i]}} for i in range(3)}
@@ -257,10 +264,11 @@ def _path_combine_labels(pa):
     return run
 
 
-def _path_surface_metrics(pa):
+def _path_surface_metrics(pa, images=None):
     from tests import comparison_restatement as CR
     a, b = CR.blob_pair((20, 24, 28), 3)
-    ia, ib = pa.image_from_array(a.astype(np.uint8), (0.9, 1.1, 2.5)), pa.image_from_array(b.astype(np.uint8), (0.9, 1.1, 2.5))
+    mk = (images or pa).image_from_array
+    ia, ib = mk(a.astype(np.uint8), (0.9, 1.1, 2.5)), mk(b.astype(np.uint8), (0.9, 1.1, 2.5))
 
     def run():
         got = pa.label.comparison.compute_surface_metrics(ia, ib)
@@ -268,9 +276,9 @@ def _path_surface_metrics(pa):
     return run
 
 
-def _path_dvh(pa):
-    from tests.test_dose import images
-    dose, labels, _ = images(pa)
+def _path_dvh(pa, images=None):
+    from tests.test_dose import images as dose_images
+    dose, labels, _ = dose_images(images or pa)
 
     def run():
         t = pa.dose.dvh_table(dose, labels)
@@ -279,11 +287,14 @@ def _path_dvh(pa):
     return run
 
 
-def _path_invert_field(pa):
+def _path_invert_field(pa, images=None):
     import torch
     from tests.test_field_inverse import make_field
     size, spacing = (33, 18, 9), (0.9, 0.9, 2.5)
-    field = pa.Image(torch.from_numpy(make_field(size, spacing)).to(pa.runtime.default_device()), spacing, (1.0, 2.0, 3.0))
+    if images is None:
+        field = pa.Image(torch.from_numpy(make_field(size, spacing)).to(pa.runtime.default_device()), spacing, (1.0, 2.0, 3.0))
+    else:
+        field = images.image_from_array(make_field(size, spacing), spacing, (1.0, 2.0, 3.0))
 
     def run():
         from platipy_amd.registration import invert_displacement_field
@@ -292,19 +303,20 @@ def _path_invert_field(pa):
     return run
 
 
-def _path_external_mask(pa):
+def _path_external_mask(pa, images=None):
     from tests.external_mask_restatement import head_phantom
-    image = pa.image_from_array(head_phantom().copy(), (0.9, 1.1, 2.5))
+    image = (images or pa).image_from_array(head_phantom().copy(), (0.9, 1.1, 2.5))
 
     def run():
         return [pa.generation.get_external_mask(image, max_hole_size=3).numpy()]
     return run
 
 
-def _path_bspline(pa):
+def _path_bspline(pa, images=None):
     from tests.test_bspline import E2E_SPACING, _e2e_pair
     fixed, _, moving, _, _ = _e2e_pair()
-    f, m = pa.Image(fixed, E2E_SPACING), pa.Image(moving, E2E_SPACING)
+    f, m = (pa.Image(fixed, E2E_SPACING), pa.Image(moving, E2E_SPACING)) if images is None else \
+        (images.image_from_array(fixed, E2E_SPACING), images.image_from_array(moving, E2E_SPACING))
 
     def run():
         out, t = pa.registration.bspline_registration(f, m, resolution_staging=[1], smooth_sigmas=[0], grid_scale_factors=[1], initial_grid_spacing=24,
