@@ -697,7 +697,8 @@ enum { PP_BSPLINE_STAT_VALID = 0, PP_BSPLINE_STAT_OUTSIDE = 1, PP_BSPLINE_STAT_M
  *   visited), gradient[3 cx cy cz]: HOST memory.  No valid sample: PP_ERR_NO_OVERLAP.
  * The direction cosines of `lattice`, `virt` and `fixed_geom` must agree (the initialiser takes them from the fixed
  * image): PP_ERR_DIRECTION otherwise, before anything is launched.  Two calls on the same inputs return identical bits.
- * Synchronises. */
+ * A refusal (PP_ERR_ARG, PP_ERR_DIRECTION, a sample beyond jitter_bound, PP_ERR_NO_OVERLAP) leaves value, stats and gradient
+ * untouched.  Synchronises. */
 int pp_bspline_metric_f32(pp_ctx* ctx, int metric, const float* fixed, const pp_geom* fixed_geom, const float* moving,
                           const pp_geom* moving_geom, const pp_geom* virt, int stride, const uint8_t* fixed_mask,
                           const uint8_t* moving_mask, const float* coefficients, const pp_geom* lattice,

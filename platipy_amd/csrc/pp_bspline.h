@@ -787,14 +787,14 @@ extern "C" int pp_bspline_metric_f32(pp_ctx* ctx, int metric, const float* fixed
   double s[BSP_NSCAL];
   rc = bsp_gather(ctx, metric, a, partial, nrows, scal, dgrad, ncp, s);
   if (rc) return rc;
-  PP_HIP(ctx, hipMemcpyAsync(gradient, dgrad, 3 * ncp * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-  PP_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  if (stats) stats[0] = s[0], stats[1] = s[7], stats[2] = s[8], stats[3] = s[9];
-  if (s[9] != (double)nsamp)
+  if (s[9] != (double)nsamp)   // (a refusal leaves value, stats and gradient as they were)
     return pp_fail(ctx, PP_ERR_ARG, "pp_bspline_metric_f32: %.0f of %zu samples visited -- a sample's jitter exceeds jitter_bound = %g voxels",
                    s[9], nsamp, jitter_bound);
   const double cnt = s[0];
   if (cnt <= 0.0) return pp_fail(ctx, PP_ERR_NO_OVERLAP, "pp_bspline_metric_f32: no valid sample points");
+  PP_HIP(ctx, hipMemcpyAsync(gradient, dgrad, 3 * ncp * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  PP_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  if (stats) stats[0] = s[0], stats[1] = s[7], stats[2] = s[8], stats[3] = s[9];
   if (metric == 0) {
     *value = s[6] / cnt;
   } else {
